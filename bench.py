@@ -1,6 +1,15 @@
 """bench.py — the reference's headline metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it uploads the
+scene, prepares the camera, settles the clock, warms up, times the K steps,
+writes the last timed frame under --dump-outputs, and prints one JSON line
+(metric, value, unit, ms_per_step, ...).  --full adds every other leg to that
+line: the cold first frame, the counted render with the roofline / HBM / VALU
+entries, the per-frame event times, the gather-alone term at N > 1, the host
+boundary, the frame costs (moving camera, progressive path) and the CPU
+baselines.
 
 Metric (BASELINE.json): Mray/s and ms/frame at 1920x1080 depth=3 on 1/2/4/8
 MI355X vs host CPU.  A step renders ONE full frame of the configured workload
@@ -382,6 +391,30 @@ def moving_camera_events(ctx, frames, dst, stream, repeats=3):
                     "camera's first frame vs the same camera's next frames"}
 
 
+DUMP_FULL_BYTES = 48_000_000      # a float32 frame up to this size is written whole
+DUMP_SAMPLE_PIXELS = 2_000_000    # else this many pixels: 32 MB of values + 16 MB of indices
+
+
+def dump_outputs(directory, frame_rgba8):
+    """--dump-outputs: what the timed path handed its caller in the last timed
+    step — the assembled RGBA8 frame (H, W, 4), bottom row first — written as
+    float32 to DIR/frame_rgba8.npy.  A frame larger than DUMP_FULL_BYTES as
+    float32 is written as a fixed, seeded sample of DUMP_SAMPLE_PIXELS pixels
+    (n, 4), with their row-major pixel indices in DIR/frame_rgba8_pixels.npy
+    (float64), so two builds dump the same pixels."""
+    import numpy as np
+
+    px = frame_rgba8.contiguous().cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    if px.size * 4 <= DUMP_FULL_BYTES:
+        np.save(os.path.join(directory, "frame_rgba8.npy"), px.astype(np.float32))
+        return
+    flat = px.reshape(-1, 4)
+    idx = np.sort(np.random.default_rng(20240607).choice(flat.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(directory, "frame_rgba8.npy"), flat[idx].astype(np.float32))
+    np.save(os.path.join(directory, "frame_rgba8_pixels.npy"), idx.astype(np.float64))
+
+
 def spawn_ranks(n: int) -> int:
     """`bench.py --gpus N` run bare: start the N ranks (one process per GPU)
     with torch.distributed.run as a child process — never an exec: this
@@ -415,10 +448,17 @@ def main():
                     help="untimed renders for this long before the warmup steps, so the timed steps run at the "
                          "GPU's sustained clock (runs of a few dozen frames measured 6-9%% slower)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes the last timed step's assembled RGBA8 frame as "
+                         "float32 to DIR/frame_rgba8.npy (a seeded pixel sample of a frame over 48 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: cold first frame, counted render with "
+                         "roofline / HBM entries, per-frame event times, the gather alone (N>1), host boundary, "
+                         "frame costs and the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-host-boundary", action="store_true",
-                    help="skip the PCIe-inclusive rt_render leg (profiling runs: only the timed launches)")
+                    help="--full: skip the PCIe-inclusive rt_render leg (profiling runs: only the timed launches)")
     ap.add_argument("--partition", default="auto", choices=["auto", "slabs", "bands"],
                     help="N>1: row slabs, cyclic 16-row bands, or bands when slabs are >10%% imbalanced")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -457,6 +497,9 @@ def main():
         sys.exit(2)
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr, flush=True)
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr, flush=True)
         sys.exit(2)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -526,8 +569,9 @@ def run_rank(args, ctx_opts, world, rank, local):
     upload_ms = (time.perf_counter() - t_up) * 1e3
     # the process's first frame (cold): upload + first synchronous render of
     # the full frame into pinned host memory
+    full = args.full
     cold = None
-    if world == 1:
+    if full and world == 1:
         pin = torch.empty((H, W, 4), dtype=torch.uint8).pin_memory()
         t_r = time.perf_counter()
         rt_amd.lib().rt_render(ctx._h, ctypes.byref(scene.frame), pin.data_ptr())
@@ -537,7 +581,7 @@ def run_rank(args, ctx_opts, world, rank, local):
         del pin
     lbinfo = None
     L = rt_amd.lib()
-    if hasattr(L, "rt_debug_lb_info"):
+    if full and hasattr(L, "rt_debug_lb_info"):
         L.rt_debug_lb_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         info = (ctypes.c_double * 64)()
         if L.rt_debug_lb_info(ctx._h, info, 64) == 0 and info[0]:
@@ -589,24 +633,31 @@ def run_rank(args, ctx_opts, world, rank, local):
                          send_channels=args.gather_channels) if use_dist else None)
     single = torch.zeros((rows, W, 4), dtype=torch.uint8, device="cuda")
 
-    # one counted render (atomics) for the algorithmic work of this rank's slab
-    sf = frame.copy()
-    sf.flags = rt_amd.FLAG_STATS
-    ctx.render(sf)
-    st = ctx.stats()
-    cbinfo = None  # the camera buffer, built by that synchronous render (per camera)
-    if hasattr(L, "rt_debug_cb_info"):
-        L.rt_debug_cb_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        ci = (ctypes.c_double * 10)()
-        if L.rt_debug_cb_info(ctx._h, ci, 10) == 0 and ci[0]:
-            cbinfo = {"entries": int(ci[1]), "build_ms": round(ci[2], 3), "tiles": int(ci[3]),
-                      "inline_records": bool(ci[4]), "build_host_ms": round(ci[5], 3),
-                      "binning": {"candidate_pairs": int(ci[6]), "lists_over_256": int(ci[7]),
-                                  "longest_list": int(ci[8]), "capacity": int(ci[9])}}
-    brute = algorithmic_flops(types, st.primary_rays, st.bounce_rays, st.shadow_rays)
-    flops = executed_flops(st)
-    brute_tests = (st.primary_rays + st.bounce_rays + st.shadow_rays) * int(types.shape[0])
-    run_tests = st.triangle_tests + st.plane_tests + st.quadric_tests
+    st, cbinfo = None, None
+    if full:
+        # one counted render (atomics) for the algorithmic work of this rank's slab
+        sf = frame.copy()
+        sf.flags = rt_amd.FLAG_STATS
+        ctx.render(sf)
+        st = ctx.stats()
+        # the camera buffer, built by that synchronous render (per camera)
+        if hasattr(L, "rt_debug_cb_info"):
+            L.rt_debug_cb_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+            ci = (ctypes.c_double * 10)()
+            if L.rt_debug_cb_info(ctx._h, ci, 10) == 0 and ci[0]:
+                cbinfo = {"entries": int(ci[1]), "build_ms": round(ci[2], 3), "tiles": int(ci[3]),
+                          "inline_records": bool(ci[4]), "build_host_ms": round(ci[5], 3),
+                          "binning": {"candidate_pairs": int(ci[6]), "lists_over_256": int(ci[7]),
+                                      "longest_list": int(ci[8]), "capacity": int(ci[9])}}
+        brute = algorithmic_flops(types, st.primary_rays, st.bounce_rays, st.shadow_rays)
+        flops = executed_flops(st)
+        brute_tests = (st.primary_rays + st.bounce_rays + st.shadow_rays) * int(types.shape[0])
+        run_tests = st.triangle_tests + st.plane_tests + st.quadric_tests
+    else:
+        # the per-camera state that synchronous render leaves (camera records,
+        # and the camera buffer where the frame's kernel uses one), without a
+        # render: the timed launches take the same path either way
+        ctx.prepare_camera(frame)
 
     counter = [0]
     # the C entry point with its arguments converted once: the Python
@@ -669,31 +720,39 @@ def run_rank(args, ctx_opts, world, rank, local):
     # masks; the timed frames read them: rt_trace_tiny<0,1,37> at C2)
     timed_kernel = ctx.stats().kernel
     frame_sha = None
-    if args.frame_sha and rank == 0:
-        import hashlib
-
+    if (args.frame_sha or args.dump_outputs) and rank == 0:
+        # the last timed step's frame, as the caller of the timed path holds it
         last = gather.frame(args.steps - 1 + args.warmup) if gather else single[:H]
-        frame_sha = hashlib.sha256(last.contiguous().cpu().numpy().tobytes()).hexdigest()
+        if args.frame_sha:
+            import hashlib
+
+            frame_sha = hashlib.sha256(last.contiguous().cpu().numpy().tobytes()).hexdigest()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
     if per_launch:
         kernel_ms = sum(a.elapsed_time(b) for a, b in events) / args.steps
     else:
         kernel_ms = events[0][0].elapsed_time(events[0][1]) / args.steps
-    # per-frame kernel times (median beside the mean): after
-    # the timed region, K more frames with an event pair around each launch
-    frame_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                for _ in range(args.steps)]
-    for a, b in frame_ev:
-        a.record()
-        ctx.render_async(frame, single.data_ptr(), 0, stream)
-        b.record()
-    torch.cuda.synchronize()
-    per_frame = sorted(a.elapsed_time(b) for a, b in frame_ev)
+    per_frame = None
+    if full:
+        # per-frame kernel times (median beside the mean): after
+        # the timed region, K more frames with an event pair around each launch
+        frame_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                    for _ in range(args.steps)]
+        for a, b in frame_ev:
+            a.record()
+            ctx.render_async(frame, single.data_ptr(), 0, stream)
+            b.record()
+        torch.cuda.synchronize()
+        per_frame = sorted(a.elapsed_time(b) for a, b in frame_ev)
     ranks_info = None
+    tot_primary = tot_bounce = tot_shadow = None
     if use_dist:
         cdev = "cuda" if args.dist_backend == "nccl" else "cpu"
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if use_dist and full:
         c = torch.tensor([st.primary_rays, st.bounce_rays, st.shadow_rays], dtype=torch.float64, device=cdev)
         dist.all_reduce(c)
         tot_primary, tot_bounce, tot_shadow = (float(x) for x in c.tolist())
@@ -725,32 +784,12 @@ def run_rank(args, ctx_opts, world, rank, local):
                               "fastest rank; gather: batches of gather_batch already-rendered slabs gathered to "
                               "rank 0 back to back with no render beside them (max over ranks, per batch); bytes: "
                               "one non-root rank's slab per frame over its link to rank 0"}
-    else:
+    elif full:
         tot_primary, tot_bounce, tot_shadow = float(st.primary_rays), float(st.bounce_rays), float(st.shadow_rays)
 
     if rank == 0:
         ms = elapsed * 1e3 / args.steps
         value = W * H * args.steps / elapsed / 1e6
-        achieved = flops / (kernel_ms * 1e-3) / 1e12
-        # Hardware counters of the same kernel on the same config, from the
-        # rocprofv3 --pmc passes committed under profiles/ (tools/pmc_summary.py):
-        # L2-to-fabric bytes per launch (read requests by size + WRITE_SIZE,
-        # calibrated in tools/calib; FETCH_SIZE x2 kept beside it) and VALU
-        # wave-instructions per launch; VALU busy = those x 2 cycles (wave64
-        # on a SIMD32) over 1,024 SIMDs x this run's kernel time at 2.4 GHz.
-        traffic, valu_busy, pmc_src, rec = None, None, None, None
-        tfile = os.path.join(REPO, "profiles", "pmc.json")
-        if os.path.exists(tfile):
-            with open(tfile) as f:
-                rec = json.load(f).get(f"{args.config}_n{world}")
-            if rec and rec.get("src_sha256") == product_src_sha256():
-                traffic = rec.get("hbm_bytes_per_launch")
-                if rec.get("SQ_INSTS_VALU"):
-                    valu_busy = round(rec["SQ_INSTS_VALU"] * 2 / (1024 * kernel_ms * 1e-3 * 2.4e9), 3)
-                pmc_src = rec.get("source")
-            elif rec:  # counters of other kernel sources: not this kernel's
-                pmc_src = "stale: " + rec.get("source", "") + " (collected on other sources)"
-        alg_bytes = 4 * W * rt_amd.frame_rows(frame) + scene_bytes
         out = {
             "metric": "Mray/s and ms/frame at 1920x1080 depth=3, 1/2/4/8 MI355X vs host CPU",
             "value": round(value, 3),
@@ -776,6 +815,42 @@ def run_rank(args, ctx_opts, world, rank, local):
                                         else " + gloo gather to rank 0 through host memory") if use_dist else ""),
                        "slab_imbalance": round(imbalance, 3) if imbalance is not None else None,
                        **({"options": ctx_opts} if ctx_opts else {})},
+            "kernel_ms": round(kernel_ms, 4),
+            # the kernel the library reports for the timed loop's last launch
+            # (rt_stats.kernel, ABI 7): the name rocprof's dominant kernel carries
+            "kernel": timed_kernel,
+            "settle": {"frames": settle_frames, "ms": round(args.settle_ms, 1),
+                       "note": "untimed renders before the warmup steps (sustained clock); then warmup, then the "
+                               "timed steps"},
+            "upload_ms": round(upload_ms, 2),
+            "full": full,
+        }
+        if frame_sha:
+            out["frame_rgba8_sha256"] = frame_sha
+        if args.dump_outputs:
+            out["dumped_outputs"] = args.dump_outputs
+    if rank == 0 and full:
+        achieved = flops / (kernel_ms * 1e-3) / 1e12
+        # Hardware counters of the same kernel on the same config, from the
+        # rocprofv3 --pmc passes committed under profiles/ (tools/pmc_summary.py):
+        # L2-to-fabric bytes per launch (read requests by size + WRITE_SIZE,
+        # calibrated in tools/calib; FETCH_SIZE x2 kept beside it) and VALU
+        # wave-instructions per launch; VALU busy = those x 2 cycles (wave64
+        # on a SIMD32) over 1,024 SIMDs x this run's kernel time at 2.4 GHz.
+        traffic, valu_busy, pmc_src, rec = None, None, None, None
+        tfile = os.path.join(REPO, "profiles", "pmc.json")
+        if os.path.exists(tfile):
+            with open(tfile) as f:
+                rec = json.load(f).get(f"{args.config}_n{world}")
+            if rec and rec.get("src_sha256") == product_src_sha256():
+                traffic = rec.get("hbm_bytes_per_launch")
+                if rec.get("SQ_INSTS_VALU"):
+                    valu_busy = round(rec["SQ_INSTS_VALU"] * 2 / (1024 * kernel_ms * 1e-3 * 2.4e9), 3)
+                pmc_src = rec.get("source")
+            elif rec:  # counters of other kernel sources: not this kernel's
+                pmc_src = "stale: " + rec.get("source", "") + " (collected on other sources)"
+        alg_bytes = 4 * W * rt_amd.frame_rows(frame) + scene_bytes
+        out.update({
             "total_rays_per_s_M": round((tot_primary + tot_bounce + tot_shadow) * args.steps / elapsed / 1e6, 3),
             "rays_per_frame": {"primary": int(tot_primary), "bounce": int(tot_bounce), "shadow": int(tot_shadow)},
             "bounce_walk": ({"triangle_tests_per_bounce_ray": round(st.bounce_triangle_tests / st.bounce_rays, 2),
@@ -784,17 +859,12 @@ def run_rank(args, ctx_opts, world, rank, local):
                              "note": "this rank's bounce rays (Scene.cpp:1779-1823): exact triangle tests and BVH "
                                      "inner nodes visited per ray (brute force: every triangle)"}
                             if st.bounce_rays else None),
-            "kernel_ms": round(kernel_ms, 4),
             "frame_ms": {"median": round(per_frame[len(per_frame) // 2], 4),
                          "mean": round(sum(per_frame) / len(per_frame), 4),
                          "p10": round(per_frame[len(per_frame) // 10], 4),
                          "p90": round(per_frame[(9 * len(per_frame)) // 10], 4), "frames": len(per_frame),
                          "note": "this rank's render of K more frames after the timed region, one HIP event pair "
                                  "around each launch (includes each launch's dispatch gap)"},
-            "settle": {"frames": settle_frames, "ms": round(args.settle_ms, 1),
-                       "note": "untimed renders before the warmup steps (sustained clock); then warmup, then the "
-                               "timed steps"},
-            "upload_ms": round(upload_ms, 2),
             "light_buffer": lbinfo,
             "camera_buffer": cbinfo,
             "hbm": {"algorithmic_bytes": int(alg_bytes), "measured_bytes": traffic,
@@ -816,11 +886,9 @@ def run_rank(args, ctx_opts, world, rank, local):
                          "work": "exact ray-primitive tests executed (after culling) x SURVEY 8(d) ops + set-up + shading",
                          "tests_executed": int(run_tests), "tests_brute_force": int(brute_tests),
                          "brute_force_equiv_tflops": round(brute / (kernel_ms * 1e-3) / 1e12, 3)},
-        }
+        })
         if ranks_info:
             out["ranks"] = ranks_info
-        if frame_sha:
-            out["frame_rgba8_sha256"] = frame_sha
         if world == 1 and not args.no_host_boundary:
             out["host_boundary"] = host_boundary(ctx, frame, W)
             fc = frame_costs(scene, frame, W, cold, ctx_opts)
@@ -844,6 +912,7 @@ def run_rank(args, ctx_opts, world, rank, local):
             ca = cpu_allcores(path, W, H, depth, max(2.0, args.cpu_seconds / 2))
             ca["gpu_over_cpu"] = round(value / ca["value"], 1) if ca["value"] else None
             out["cpu_baseline_allcores"] = ca
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

@@ -30,7 +30,7 @@ def _port():
 
 def _bench(n, config, partition="auto", gather_batch=4, gather_channels=3):
     args = ["bench.py", "--gpus", str(n), "--steps", "3", "--warmup", "1", "--config", config, "--frame-sha",
-            "--no-cpu-baseline", "--no-host-boundary"]
+            "--full", "--no-cpu-baseline", "--no-host-boundary"]
     if n > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", str(n),
                "--master-addr", "127.0.0.1", "--master-port", str(_port())] + args + [
@@ -191,7 +191,7 @@ def test_bench_nccl_one_rank_runs_the_rccl_path(one_rank):
     init_process_group("nccl", device_id=...), the CUDA-tensor all-reduces and
     the RootGather path, with the frame byte-identical to the plain run."""
     args = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "c2", "--frame-sha",
-            "--no-cpu-baseline", "--no-host-boundary", "--force-dist", "--dist-backend", "nccl"]
+            "--full", "--no-cpu-baseline", "--no-host-boundary", "--force-dist", "--dist-backend", "nccl"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_port())] + args
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")

@@ -158,7 +158,7 @@ def test_small_big_list_frames_walk_two_entries_per_round(golden_images, c3_colu
 
 
 @pytest.mark.parametrize("mode,stripe", [(0, 0), (2, 0), (2, 3), (2, 4), (3, 0)])
-def test_xcd_deal_modes_render_the_same(golden_images, c3_column, heightfield_path, mode, stripe):
+def test_xcd_deal_modes_render_the_same(golden_images, c3_column, heightfield_path, tmp_path, mode, stripe):
     """RT_OPT_XCD_DEAL: the big-list kernels' tile-to-XCD dealing (padded
     grids in modes 2 and 3) only moves tiles between workgroups: C3 at full
     size against the reference's windows, a slab off the tile grid, a band
@@ -187,7 +187,7 @@ def test_xcd_deal_modes_render_the_same(golden_images, c3_column, heightfield_pa
     frames.append(f)
     for f in frames:
         assert bits_equal(b.render_float(f), a.render_float(f))
-    hf = synth.write_heightfield("/tmp/rt_amd_xcd_hfr.dat", cols=60, rows=30, reflect=0.5)
+    hf = synth.write_heightfield(str(tmp_path / "rt_amd_xcd_hfr.dat"), cols=60, rows=30, reflect=0.5)
     s2 = rt_amd.Scene(hf, 1920, 1080, 3)
     for c in (a, b):
         c.upload(s2)

@@ -23,12 +23,12 @@ for s in $STEPS; do
     tests) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q -rA --timeout 300 --timeout-method thread ;;
     tests_k) run pytest_gpu_k 600 python -u -m pytest tests -m gpu -x -v -rA --timeout 300 --timeout-method thread -k "$TESTK" ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 400 python bench.py ;;
+    bench) run bench 400 python bench.py --full ;;
     bench_all)
-      for c in ${CONFIGS:-c1 c2 c3 c4 c4s7 c4s9 c5 c3r c5r}; do run bench_$c 400 python bench.py --config $c --cpu-seconds 5; done ;;
+      for c in ${CONFIGS:-c1 c2 c3 c4 c4s7 c4s9 c5 c3r c5r}; do run bench_$c 400 python bench.py --full --config $c --cpu-seconds 5; done ;;
     bench_big)
-      for c in ${CONFIGS:-c3 c5}; do run bench_$c 400 python bench.py --config $c --steps 10 --no-cpu-baseline; done ;;
-    bench_one) run bench_${CONFIG:-c2} 400 python bench.py --config ${CONFIG:-c2} --steps 20 --no-cpu-baseline ;;
+      for c in ${CONFIGS:-c3 c5}; do run bench_$c 400 python bench.py --full --config $c --steps 10 --no-cpu-baseline; done ;;
+    bench_one) run bench_${CONFIG:-c2} 400 python bench.py --full --config ${CONFIG:-c2} --steps 20 --no-cpu-baseline ;;
     listpmc) run list_counters 120 rocprofv3 -L ;;
     pmc)
       B="python bench.py --steps 5 --warmup 1 --settle-ms 0 --no-cpu-baseline --no-host-boundary --config ${CONFIG:-c2}"

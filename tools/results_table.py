@@ -1,6 +1,6 @@
-"""Markdown rows of DESIGN.md §6 from bench.py logs (one JSON line each).
+"""Markdown rows of DESIGN.md §6 from `bench.py --full` logs (one JSON line each).
 
-    python tools/results_table.py gpurun_out/bench_c1.log gpurun_out/bench_c2.log ...
+    python tools/results_table.py bench_c1.log bench_c2.log ...
 """
 import json
 import sys
