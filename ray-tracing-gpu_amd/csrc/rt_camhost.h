@@ -205,11 +205,13 @@ static bool tile_cone(const rt_frame* f, float& cosW, float& sinW, float& chord)
 // ---- camera records in the launch (tiny scenes; rt_cull.h TinyCam)
 // Used for depth-0 frames of scenes of 1..kTinyMax triangles whose shadow
 // rays go through the light buffer (RT_OPT_LAUNCH_CAMERA, on by default):
-// then nothing per camera lives on the device.
+// then nothing per camera lives on the device.  The kernels read their
+// lights from the upload's light records (d_lrec, built beside the light
+// buffer); any other frame takes the general kernels.
 static bool tiny_ok(const rt_ctx* c, int depth, bool lbuf)
 {
     return c->opt_launch_camera && depth == 0 && lbuf && c->n_tri > 0 && c->n_tri <= kTinyMax &&
-           (int)c->h_tri.size() == 3 * c->n_tri;
+           (int)c->h_tri.size() == 3 * c->n_tri && c->d_lrec && c->shadow_split;
 }
 
 // One mask half-space of rt_cull.h tiny_tile_mask: dot(w, p.xyz) >= p.w,

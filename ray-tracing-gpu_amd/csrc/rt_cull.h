@@ -442,6 +442,67 @@ struct TinyCam {
     float4 rec[8 * kTinyMax];
 };
 
+// The launch record of rt_trace_tiny: everything wave-uniform the kernel
+// reads arrives with the launch as ONE by-value argument, a compact header
+// in front of the camera records.  The kernel loads the header's first part
+// (camera, frame, mask and plane fields) unconditionally at its top, under
+// one wait, and issues the tile's mask load behind it (its pointer, then
+// the mask: pinning the pointer too measured slower); the scene
+// part (pointers and counts of the shading) is one contiguous block.  The
+// FrameDev / SceneDev the shared device functions take are rebuilt from it
+// in registers (rt_trace_tiny): fields it does not carry are zero and never
+// read by a depth-0 small-list kernel.
+// Planes: for the first kTinyPlanes planes of plane[] (opaque ones first, as
+// plane[] holds them) the header carries the record [n cst], the file index
+// and the camera-ray constant num = n . O + cst, computed on the host in
+// float with hit_plane's operation order — the camera is the origin of every
+// primary ray, so the per-lane sum was the same value in every lane.  The
+// shadow rays' opaque-plane tests read the same records, so they stay in
+// SGPRs across the lights.  Planes past kTinyPlanes take the loops over
+// plane[].  (Quadrics: hit_quadric's C and the three o-only sums inside B are
+// wave-uniform for camera rays too and could be carried the same way without
+// changing a bit; the reference's tiny scenes have at most one quadric and
+// the timed scene none, so they are left to the per-lane code.)
+constexpr int kTinyPlanes = 2;
+struct TinyHead {
+    // ---- camera / frame / masks (loaded at the top of the kernel)
+    float cam[3];
+    int width;
+    float orient[12];  // rows 0..3, columns 0..2 of the orientation (all camera_dir reads)
+    float half_w, half_h, inv_w, inv_h;
+    float bg[3];
+    int height;
+    int row_begin, row_end, band_rows, band_count;
+    int band_index, flags, n, masked;  // n, masked: TinyCam's
+    unsigned* mask;                    // TinyCam's mask (tiles_x below)
+    int tiles_x, n_plane;
+    float4 plane[kTinyPlanes];  // [n cst]
+    float pnum[kTinyPlanes];    // n . O + cst
+    int pidx[kTinyPlanes];      // file index
+    unsigned* rgba;
+    float* rgbf;
+    // ---- scene (the shading's pointers and counts)
+    const float4* geom;
+    const float4* mat;
+    const float4* lrec;  // 64-byte light-shade records (rt_shade.h kLightRec)
+    const float4* planes;
+    const float4* quad;
+    const int* translucent;
+    const unsigned* lb_off;
+    const float4* lb_ent;
+    const float4* lb_dcap;
+    const float4* cone_light;
+    const float4* tri;
+    StatsDev* stats;
+    int n_lights, n_tri, n_tri_opaque, n_plane_opaque;
+    int n_quad, n_quad_opaque, n_translucent, shadow_split;
+};
+struct TinyLaunch {
+    TinyHead h;
+    // per triangle, nearest first: TinyCam's records
+    float4 rec[8 * kTinyMax];
+};
+
 // The tile's mask, computed by the wave: lane j < n tests triangle j against
 // the tile cone around lane 36's direction (full wave: depth-0 kernels run
 // every lane).  The camera wave test (cone_overlap, edges_open) at the fixed
@@ -456,17 +517,17 @@ struct TinyLane {
 };
 // Only the lanes of listed triangles load (each wave reads n x 64 B through
 // its CU's L1, not 64 x 64 B: A/B -1.4% on a moving C2 camera).
-__device__ __forceinline__ TinyLane tiny_lane_load(const TinyCam& T)
+__device__ __forceinline__ TinyLane tiny_lane_load(int n, const float4* rec)
 {
     const int lane = (int)(threadIdx.x & 63);
     TinyLane L{};
-    if (lane < T.n) {
-        const float4* r = T.rec + 8 * lane;
+    if (lane < n) {
+        const float4* r = rec + 8 * lane;
         L = TinyLane{{r[0], r[1], r[2], r[3]}};
     }
     return L;
 }
-__device__ __forceinline__ unsigned tiny_tile_mask(const TinyCam& T, const TinyLane& L, const Vec3 D)
+__device__ __forceinline__ unsigned tiny_tile_mask(int n, const TinyLane& L, const Vec3 D)
 {
     typedef float f2 __attribute__((ext_vector_type(2)));
     const float wx = readlanef(D.x, 36), wy = readlanef(D.y, 36), wz = readlanef(D.z, 36);
@@ -476,32 +537,40 @@ __device__ __forceinline__ unsigned tiny_tile_mask(const TinyCam& T, const TinyL
     b = __builtin_elementwise_fma(Y, f2{L.q[2].z, L.q[2].w}, b);
     a = __builtin_elementwise_fma(X, f2{L.q[0].x, L.q[0].y}, a);
     b = __builtin_elementwise_fma(X, f2{L.q[2].x, L.q[2].y}, b);
-    const bool keep = ((int)(threadIdx.x & 63) < T.n) & (a.x >= L.q[1].z) & (a.y >= L.q[1].w) & (b.x >= L.q[3].z) &
+    const bool keep = ((int)(threadIdx.x & 63) < n) & (a.x >= L.q[1].z) & (a.y >= L.q[1].w) & (b.x >= L.q[3].z) &
                       (b.y >= L.q[3].w);
     return (unsigned)__ballot(keep);
 }
 
+// The launch record's planes as the device functions take them.
+struct TinyPlanes {
+    float4 a[kTinyPlanes];  // [n cst]
+    float num[kTinyPlanes];
+    int idx[kTinyPlanes];
+};
+
 // Closest hit for camera rays from the launch's records: planes and quadrics
-// first, then the tile's kept triangles nearest first (tile < 0 or no masks:
-// every listed triangle), leaving once every lane holds a hit nearer than
-// the next dmin (t >= dmin > best: no later triangle can win or tie).
-// SELF: the wave computed the tile's mask (tmask, tiny_tile_mask); else it
-// reads the stored one.
-template <bool SELF>
-__device__ __forceinline__ int closest_hit_camera_tiny(const SceneDev& S, const TinyCam& T, int tile, unsigned tmask,
-                                                       const Vec3 O, const Vec3 D, float& best_t, Counters& cnt)
+// first, then the tile's kept triangles (mask m) nearest first, leaving once
+// every lane holds a hit nearer than the next dmin (t >= dmin > best: no
+// later triangle can win or tie).  The first kTinyPlanes planes are tested
+// with the host's n . O + cst (Plan.cpp:128-144 with that sum read instead
+// of recomputed: the same division, the same t).
+__device__ __forceinline__ int closest_hit_camera_tiny(const SceneDev& S, const TinyPlanes& PL, const float4* rec,
+                                                       unsigned m, const Vec3 O, const Vec3 D, float& best_t,
+                                                       Counters& cnt)
 {
-    unsigned m = T.n >= 32 ? ~0u : (1u << T.n) - 1u;
-    if (T.masked && tile >= 0) {
-        if constexpr (SELF) {
-            m = tmask;
-        } else {
-            m = T.mask[tile];  // wave-uniform (scalar) load
-        }
-    }
     float bt = -1.0f;
     int bi = -1;
-    for (int k = 0; k < S.n_plane; ++k) {
+#pragma unroll
+    for (int k = 0; k < kTinyPlanes; ++k) {
+        if (k < S.n_plane) {
+            ++cnt.pla;
+            const float vd = dot(make3(PL.a[k].x, PL.a[k].y, PL.a[k].z), D);
+            const float t = -PL.num[k] / vd;
+            take_min(fabsf(vd) > kEps, t, PL.idx[k], bt, bi);
+        }
+    }
+    for (int k = kTinyPlanes; k < S.n_plane; ++k) {
         const float4 a = S.plane[2 * k], b = S.plane[2 * k + 1];
         float t;
         ++cnt.pla;
@@ -520,7 +589,7 @@ __device__ __forceinline__ int closest_hit_camera_tiny(const SceneDev& S, const 
     while (m) {
         const int j = (int)__builtin_ctz(m);
         m &= m - 1u;
-        const float4* r = T.rec + 8 * j + 4;
+        const float4* r = rec + 8 * j + 4;
         const float4 d = r[3];
         if (!__any((bi < 0) | !(bt < d.z))) break;
         camera_tri(r[0], r[1], r[2], d, D, bt, bi, cnt);
@@ -535,10 +604,8 @@ __device__ __forceinline__ int closest_hit_camera_tiny(const SceneDev& S, const 
 // tile >= 0: the wave is that camera-buffer tile (WAVE bit 8).
 template <int WAVE>
 __device__ __forceinline__ int closest_hit_primary(const SceneDev& S, const Vec3 O, const Vec3 D, float& t,
-                                                   Counters& cnt, int tile = -1, const TinyCam* T = nullptr,
-                                                   unsigned tmask = 0)
+                                                   Counters& cnt, int tile = -1)
 {
-    if constexpr ((WAVE & 32) != 0) return closest_hit_camera_tiny<(WAVE & 64) != 0>(S, *T, tile, tmask, O, D, t, cnt);
     if ((WAVE & 8) && tile >= 0 && wave_full())
         return closest_hit_camera_list<(WAVE & 2) != 0>(S, tile, O, D, t, cnt);
     if ((WAVE & 3) > 0 && wave_full()) {

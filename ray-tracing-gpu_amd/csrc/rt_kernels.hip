@@ -69,13 +69,13 @@ struct Refr {
 // its colour (deferred: rt_wf_fold writes the pixel).
 template <int MAXD, int LB, int WAVE>
 __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, Counters& cnt, bool live, int tile,
-                          const TinyCam* T, unsigned tmask, unsigned pix, bool& deferred, unsigned chunk)
+                          unsigned pix, bool& deferred, unsigned chunk)
 {
     const Color bg{F.bg[0], F.bg[1], F.bg[2]};
     if constexpr (MAXD == 0) {
         float t;
         RT_MARK(cnt, 0);
-        const int idx = closest_hit_primary<(WAVE & 107)>(S, O, D, t, cnt, tile, T, tmask);
+        const int idx = closest_hit_primary<(WAVE & 107)>(S, O, D, t, cnt, tile);
         RT_MARK(cnt, 1);
         // Lanes that miss (or lie outside the frame) stay in step through the
         // shading so the wave stays whole for wave-level shadow culling.
@@ -120,7 +120,7 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
             float t;
             int idx;
             if (lv == 0)
-                idx = closest_hit_primary<(WAVE & 107)>(S, O, D, t, cnt, tile, T);
+                idx = closest_hit_primary<(WAVE & 107)>(S, O, D, t, cnt, tile);
             else if constexpr ((WAVE & 256) != 0)  // bounce rays through the BVH (rt_bvh.h)
                 idx = closest_hit_bvh(S, O, D, t, cnt);
             else
@@ -172,7 +172,7 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
                 float t;
                 int idx;
                 if (camera_ray)
-                    idx = closest_hit_primary<(WAVE & 107)>(S, O, D, t, cnt, tile, T);
+                    idx = closest_hit_primary<(WAVE & 107)>(S, O, D, t, cnt, tile);
                 else if constexpr ((WAVE & 256) != 0)  // bounce rays through the BVH (rt_bvh.h)
                     idx = closest_hit_bvh(S, O, D, t, cnt);
                 else
@@ -277,13 +277,10 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
 // The launch-camera kernel that computes its tile masks (WAVE bit 64) is
 // held to 64 VGPRs, 8 waves/SIMD (A/B, moving C2 camera: -2.3% against 7;
 // the mask-reading kernel fits 58 VGPRs anyway, and asked for 8 measured
-// +2.4% static).  RT_TINY_HOIST: its mask planes are loaded at the top of
-// the kernel (A/B: -2.7% against loading them where the mask is computed).
+// +2.4% static).  Its mask planes are loaded at the top of the kernel (A/B:
+// -2.7% against loading them where the mask is computed).
 #ifndef RT_WAVES_PER_EU_TINY
 #define RT_WAVES_PER_EU_TINY 8
-#endif
-#ifndef RT_TINY_HOIST
-#define RT_TINY_HOIST 1
 #endif
 constexpr int waves_per_eu(int maxd, int wave)
 {
@@ -294,11 +291,9 @@ constexpr int waves_per_eu(int maxd, int wave)
 // One 8 x 8 tile (the body of both trace kernels below).
 // COUNT: also tally the exact tests executed (the RT_FLAG_STATS launch); in
 // the timed kernels the tallies are dead and compile away.
-// T: the launch's camera records (WAVE bit 32, rt_trace_tiny), else nullptr.
 template <int MAXD, int LB, int WAVE, bool COUNT>
 __device__ __forceinline__ void trace_tile(const SceneDev& S, const FrameDev& F, unsigned* __restrict__ rgba,
-                                           float* __restrict__ rgbf, StatsDev* __restrict__ stats, const TinyCam* T,
-                                           int bx, int by)
+                                           float* __restrict__ rgbf, StatsDev* __restrict__ stats, int bx, int by)
 {
     const int lane = threadIdx.x & 63;
     // XCD-aware block order: the dispatcher deals workgroups round-robin over
@@ -326,8 +321,6 @@ __device__ __forceinline__ void trace_tile(const SceneDev& S, const FrameDev& F,
     cnt.last = __builtin_amdgcn_s_memtime();
 #endif
     Color c{0.f, 0.f, 0.f};
-    TinyLane tl;
-    if constexpr ((WAVE & 64) != 0 && RT_TINY_HOIST) tl = tiny_lane_load(*T);  // the mask's records, in flight under the set-up
     // Without bounces every lane runs (lanes outside the frame on a clamped
     // pixel, result dropped) so edge waves stay whole for wave-level culling.
     if (MAXD == 0 || valid) {
@@ -336,21 +329,17 @@ __device__ __forceinline__ void trace_tile(const SceneDev& S, const FrameDev& F,
         const Vec3 D = camera_dir(F, pxc, pyc);
         const Vec3 O = make3(F.cam[0], F.cam[1], F.cam[2]);
         cnt.primary = valid ? 1u : 0u;
-        // camera-buffer tile (or the launch records' tile): this wave's 8
-        // rows must be one tile row of the full frame (the lists and boxes
-        // hold for its lanes' clamped pixels, a superset of the wave's)
+        // camera-buffer tile: this wave's 8 rows must be one tile row of the
+        // full frame (the lists and boxes hold for its lanes' clamped pixels,
+        // a superset of the wave's)
         int tile = -1;
         if ((WAVE & 8) && S.cb_tiles_x > 0 && (py0 & 7) == 0) {
             tile = (py0 >> 3) * S.cb_tiles_x + tile_x;
             if (S.cb_flag[tile]) tile = -1;
         }
-        unsigned tmask = 0;
-        if ((WAVE & 32) && (py0 & 7) == 0) tile = (py0 >> 3) * T->tiles_x + tile_x;
-        if constexpr ((WAVE & 64) != 0 && !RT_TINY_HOIST) tl = tiny_lane_load(*T);
-        if constexpr ((WAVE & 64) != 0) tmask = tiny_tile_mask(*T, tl, D);
         const size_t o = (size_t)ly * F.width + px;
         bool deferred = false;
-        c = radiance<MAXD, LB, WAVE>(S, F, O, D, cnt, valid, tile, T, tmask, (unsigned)o, deferred,
+        c = radiance<MAXD, LB, WAVE>(S, F, O, D, cnt, valid, tile, (unsigned)o, deferred,
                                      (unsigned)(by * F.tiles_x + bx));
         if (valid & !deferred) {
             if (rgbf) {
@@ -371,11 +360,6 @@ __device__ __forceinline__ void trace_tile(const SceneDev& S, const FrameDev& F,
                 else rgba[o] = px8;
             }
         }
-        // the tile's mask for its camera's later frames on this stream (WAVE
-        // bit 128), stored last: at the top of the kernel the store's
-        // completion held up the loads behind it (A/B: C2 -2.8%, C4 -2.5%)
-        if constexpr ((WAVE & 128) != 0)
-            if (lane == 0 && T->masked && tile >= 0) T->mask[tile] = tmask;
     }
 #ifdef RT_PROF
     RT_MARK(cnt, 6);
@@ -482,19 +466,197 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
 {
     int bx, by;
     if (!tile_of_block<WAVE>(F, bx, by)) return;
-    trace_tile<MAXD, LB, WAVE, COUNT>(S, F, rgba, rgbf, stats, nullptr, bx, by);
+    trace_tile<MAXD, LB, WAVE, COUNT>(S, F, rgba, rgbf, stats, bx, by);
 }
 
-// Tiny scenes (WAVE bit 32): the camera records come with the launch
-// (TinyCam by value, read from the kernel-argument segment by scalar loads).
+// Passes the (32-bit, wave-uniform) values through scalar registers at this
+// point of the program: their loads from the kernel-argument segment are
+// issued above it, together, and waited for once, instead of where control
+// flow first uses each.  Not volatile and without a memory clobber: an
+// opaque move, no memory effect (a volatile one would bar every later
+// wave-uniform load from the scalar cache).
+#define RT_PIN4(a, b, c, d) asm("" : "+s"(a), "+s"(b), "+s"(c), "+s"(d))
+
+// Tiny scenes (WAVE bit 32): one 8 x 8 tile of a depth-0 frame whose
+// wave-uniform inputs all come with the launch (rt_cull.h TinyLaunch, one
+// by-value argument read from the kernel-argument segment by scalar loads).
+// trace_tile's frame geometry, radiance<0>'s hit and store, with the
+// dependent scalar round trips of a tile cut to: the header, the tile's mask
+// (issued straight behind it, in flight under the ray set-up), one per kept
+// triangle, the hit's normal and material, and per light its record, its
+// cell's offsets and one per entry.
+// WAVE bit 64: the wave computes the tile's mask; bit 128: and stores it.
 template <int MAXD, int LB, int WAVE, bool COUNT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu(MAXD, WAVE)))) void rt_trace_tiny(
-    const SceneDev S, const FrameDev F, const TinyCam T, unsigned* __restrict__ rgba, float* __restrict__ rgbf,
-    StatsDev* __restrict__ stats)
+    const TinyLaunch L)
 {
-    int bx, by;
-    if (!tile_of_block<WAVE>(F, bx, by)) return;
-    trace_tile<MAXD, LB, WAVE, COUNT>(S, F, rgba, rgbf, stats, &T, bx, by);
+    static_assert(MAXD == 0 && LB == 1 && (WAVE & 37) == 37, "the launch-camera kernels are depth-0, light-buffer");
+    const TinyHead& H = L.h;
+    // ---- the header's camera / frame / mask / plane part, under one wait
+    FrameDev F{};
+    F.cam[0] = H.cam[0], F.cam[1] = H.cam[1], F.cam[2] = H.cam[2];
+    F.width = H.width;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        F.orient[4 * i] = H.orient[3 * i];
+        F.orient[4 * i + 1] = H.orient[3 * i + 1];
+        F.orient[4 * i + 2] = H.orient[3 * i + 2];
+    }
+    F.half_w = H.half_w, F.half_h = H.half_h, F.inv_w = H.inv_w, F.inv_h = H.inv_h;
+    F.bg[0] = H.bg[0], F.bg[1] = H.bg[1], F.bg[2] = H.bg[2];
+    F.height = H.height;
+    F.row_begin = H.row_begin, F.row_end = H.row_end;
+    F.band_rows = H.band_rows, F.band_count = H.band_count, F.band_index = H.band_index;
+    F.flags = H.flags;
+    int tn = H.n, masked = H.masked, tiles_x = H.tiles_x;
+    unsigned* const mask = H.mask;
+    TinyPlanes PL;
+#pragma unroll
+    for (int k = 0; k < kTinyPlanes; ++k) {
+        PL.a[k] = H.plane[k];
+        PL.num[k] = H.pnum[k];
+        PL.idx[k] = H.pidx[k];
+    }
+    int n_plane = H.n_plane;
+    RT_PIN4(F.cam[0], F.cam[1], F.cam[2], F.width);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) RT_PIN4(F.orient[4 * i], F.orient[4 * i + 1], F.orient[4 * i + 2], F.half_w);
+    RT_PIN4(F.half_h, F.inv_w, F.inv_h, F.height);
+    RT_PIN4(F.row_begin, F.row_end, F.band_rows, F.band_count);
+    RT_PIN4(F.band_index, tn, masked, tiles_x);
+    RT_PIN4(n_plane, F.bg[0], F.bg[1], F.bg[2]);
+#pragma unroll
+    for (int k = 0; k < kTinyPlanes; ++k) {
+        RT_PIN4(PL.a[k].x, PL.a[k].y, PL.a[k].z, PL.a[k].w);
+        RT_PIN4(PL.num[k], PL.idx[k], tn, masked);
+    }
+
+    const int lane = threadIdx.x & 63;
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;  // hardware order (tile_of_block: small lists)
+    const int px = bx * 8 + (lane & 7);
+    const int ly0 = by * 8;  // the wave's first output row
+    const int ly = ly0 + (lane >> 3);
+    int py0 = F.row_begin + ly0, rend = F.row_end;
+    if (F.band_rows > 0) {
+        py0 = ((ly0 / F.band_rows) * F.band_count + F.band_index) * F.band_rows + ly0 % F.band_rows;
+        rend = F.height;
+    }
+    if (py0 >= rend) return;  // the whole wave lies past the frame (wave-uniform)
+    // the launch records' tile: this wave's 8 rows must be one tile row of
+    // the full frame (the masks hold for its lanes' clamped pixels)
+    const int tile = (py0 & 7) == 0 ? (py0 >> 3) * tiles_x + bx : -1;
+    const bool tiled = masked && tile >= 0;
+    unsigned tm = tn >= 32 ? ~0u : (1u << tn) - 1u;  // no masks: every listed triangle
+    if constexpr ((WAVE & 64) == 0)
+        if (tiled) tm = mask[tile];  // wave-uniform (scalar) load, waited for at the triangles
+    TinyLane tl;
+    if constexpr ((WAVE & 64) != 0) tl = tiny_lane_load(tn, L.rec);  // the mask's records, in flight under the set-up
+    const int py = py0 + (lane >> 3);
+    const bool valid = px < F.width && py < rend;
+
+    Counters cnt;
+#ifdef RT_PROF
+    cnt.last = __builtin_amdgcn_s_memtime();
+#endif
+    // every lane runs (lanes outside the frame on a clamped pixel, result
+    // dropped) so edge waves stay whole
+    const int pxc = px < F.width ? px : F.width - 1;
+    const int pyc = py < rend ? py : rend - 1;
+    const Vec3 D = camera_dir(F, pxc, pyc);
+    const Vec3 O = make3(F.cam[0], F.cam[1], F.cam[2]);
+    cnt.primary = valid ? 1u : 0u;
+    unsigned tmask = 0;
+    if constexpr ((WAVE & 64) != 0) {
+        tmask = tiny_tile_mask(tn, tl, D);
+        if (tiled) tm = tmask;
+    }
+    // ---- the scene part of the header (one contiguous block)
+    SceneDev S{};
+    S.geom = H.geom, S.mat = H.mat;
+    S.plane = H.planes, S.quad = H.quad, S.translucent = H.translucent;
+    S.lb_off = H.lb_off, S.lb_ent = H.lb_ent, S.lb_dcap = H.lb_dcap, S.cone_light = H.cone_light, S.tri = H.tri;
+    S.n_lights = H.n_lights, S.n_tri = H.n_tri, S.n_tri_opaque = H.n_tri_opaque;
+    S.n_plane = n_plane, S.n_plane_opaque = H.n_plane_opaque;
+    S.n_quad = H.n_quad, S.n_quad_opaque = H.n_quad_opaque, S.n_translucent = H.n_translucent;
+    S.shadow_split = H.shadow_split;
+
+    const Color bg{F.bg[0], F.bg[1], F.bg[2]};
+    Color c = bg;
+    float t;
+    RT_MARK(cnt, 0);
+    const int idx = closest_hit_camera_tiny(S, PL, L.rec, tm, O, D, t, cnt);
+    RT_MARK(cnt, 1);
+    // Lanes that miss (or lie outside the frame) stay in step through the
+    // shading so the wave stays whole.
+    const bool hit = idx >= 0;
+    if (__any(hit & valid)) {
+        const int sidx = hit ? idx : 0;
+        // A tile usually sees one surface: then its normal and material
+        // records come by scalar (broadcast) loads instead of a per-lane gather.
+        const int s0 = __builtin_amdgcn_readfirstlane(sidx);
+        Vec3 N;
+        Mat m;
+        if (__all(sidx == s0)) {
+            m = load_mat(S, s0);
+            N = hit_normal(S, s0, O, D, t);
+        } else {
+            m = load_mat(S, sidx);
+            N = hit_normal(S, sidx, O, D, t);
+        }
+        const Vec3 P = O + t * D;
+        const Color cl = shade_local_tiny(S, PL, H.lrec, m, P, N, D, cnt, hit & valid);
+        c = hit ? cl : bg;
+    }
+    if (valid) {
+        const size_t o = (size_t)ly * F.width + px;
+        float* const rgbf = H.rgbf;
+        unsigned* const rgba = H.rgba;
+        if (rgbf) {
+            rgbf[3 * o] = c.r;
+            rgbf[3 * o + 1] = c.g;
+            rgbf[3 * o + 2] = c.b;
+        }
+        // nontemporal (streaming) stores, as every small-list kernel (trace_tile)
+        if (rgba)
+            __builtin_nontemporal_store(unorm8(c.r) | (unorm8(c.g) << 8) | (unorm8(c.b) << 16) | 0xFF000000u, rgba + o);
+    }
+    // the tile's mask for its camera's later frames on this stream (WAVE
+    // bit 128), stored last: at the top of the kernel the store's
+    // completion held up the loads behind it (A/B: C2 -2.8%, C4 -2.5%)
+    if constexpr ((WAVE & 128) != 0)
+        if (lane == 0 && tiled) mask[tile] = tmask;
+#ifdef RT_PROF
+    RT_MARK(cnt, 6);
+    if (lane == 0) {  // the section clocks and per-tile record, as trace_tile
+        unsigned long long tot = 0;
+        for (int i = 0; i < 8; ++i) {
+            atomicAdd(&rt_prof_acc[i], cnt.pt[i]);
+            atomicAdd(&rt_prof_ev[i], (unsigned long long)cnt.ev[i]);
+            tot += cnt.pt[i];
+        }
+        const int ptile = (int)(blockIdx.y * gridDim.x + blockIdx.x);
+        if (rt_prof_tiles && ptile < rt_prof_ntiles) {
+            unsigned* o = rt_prof_tiles + 16 * (size_t)ptile;
+            o[0] = (unsigned)tot;
+            o[1] = (unsigned)(tot >> 32);
+            for (int i = 0; i < 8; ++i) o[2 + i] = (unsigned)(cnt.pt[i] >> 8);
+            const int evi[6] = {1, 2, 4, 5, 6, 7};
+            for (int i = 0; i < 6; ++i) o[10 + i] = cnt.ev[evi[i]];
+        }
+    }
+#endif
+    if (COUNT && (F.flags & RT_FLAG_STATS)) {  // the RT_FLAG_STATS launch's tallies (trace_tile)
+        unsigned long long v[9] = {cnt.primary, cnt.bounce, cnt.shadow, cnt.skipped, cnt.tri,
+                                   cnt.pla,     cnt.qua,    cnt.btri,   cnt.bnode};
+        StatsDev* sl = H.stats + ((blockIdx.x + blockIdx.y * gridDim.x) % kStatSlots);
+        unsigned long long* dst[9] = {&sl->primary, &sl->bounce, &sl->shadow, &sl->skipped, &sl->tri,
+                                      &sl->pla,     &sl->qua,    &sl->btri,   &sl->bnode};
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {  // one atomic per counter per wave (every lane runs)
+            const unsigned long long w = wave_sum_u64(v[i]);
+            if (lane == 0) atomicAdd(dst[i], w);
+        }
+    }
 }
 
 // Compiled bounce-stack capacities.  The host picks the smallest one that
@@ -701,6 +863,11 @@ struct rt_ctx {
     float4* d_lb_ent = nullptr;
     float4* d_lb_dcap = nullptr;
     float4* d_lb_meta = nullptr;
+    // the launch-camera kernels' per-light records (rt_shade.h kLightRec) and
+    // the host copies they and the launch record are made from
+    float4* d_lrec = nullptr;
+    std::vector<float4> h_lb_meta;
+    std::vector<float> h_plane;  // plane[]: [n cst] [file index 0 0 0] per plane
     bool lb_ready = false;
     int lb_levels = 0;  // buffers per light: slot = level * n_lights + light
     int lb_r0 = 0;      // light 0's first buffer's resolution (cells per face edge)
@@ -1097,6 +1264,7 @@ RT_EXPORT void rt_destroy(rt_ctx* c)
     hipFree(c->d_lb_ent);
     hipFree(c->d_lb_dcap);
     hipFree(c->d_lb_meta);
+    hipFree(c->d_lrec);
     hipFree(c->d_uni);
     hipFree(c->d_bvh_node);
     hipFree(c->d_bvh_tri);
@@ -1480,6 +1648,7 @@ static int lb_build(rt_ctx* c, int ntr, int n_opaque, const std::vector<const fl
         }
         LB_TRY(hipMemcpyAsync(c->d_lb_meta, meta.data(), meta.size() * sizeof(float4), hipMemcpyHostToDevice, st));
         LB_TRY(hipStreamSynchronize(st));  // meta (host) outlives the copy; the temporaries are freed below
+        c->h_lb_meta = meta;  // (the light records are made from it, light_records)
         mark(4);
         c->lb_ready = true;
         c->lb_entries = total;
@@ -1643,8 +1812,10 @@ RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
     hipFree(c->d_lb_ent);
     hipFree(c->d_lb_dcap);
     hipFree(c->d_lb_meta);
+    hipFree(c->d_lrec);
     c->d_lb_off = nullptr;
-    c->d_lb_ent = c->d_lb_dcap = c->d_lb_meta = nullptr;
+    c->d_lb_ent = c->d_lb_dcap = c->d_lb_meta = c->d_lrec = nullptr;
+    c->h_lb_meta.clear();
     c->lb_ready = false;
     c->lb_levels = 0;
     c->lb_r0 = 0;
@@ -1899,6 +2070,22 @@ RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
     HIP_TRY(c, hipMemcpy(c->d_geom, geom.data(), geom.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_mat, mat.data(), mat.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_lights, lig.data(), lig.size() * sizeof(float), hipMemcpyHostToDevice));
+    // The launch-camera kernels' light records (rt_shade.h): per light its
+    // lights[] pair and its first buffer's lb_meta pair in 64 bytes,
+    // [x y z I] [r g b dcov] [off base, dcap base, n dcap, R] [0 0 0 0].
+    c->h_plane = pla;
+    if (c->lb_ready && ntr <= (size_t)kTinyMax && c->h_lb_meta.size() >= 2 * (size_t)nl) {
+        std::vector<float4> lr((size_t)kLightRec * nl);
+        for (int j = 0; j < nl; ++j) {
+            const float* l = &lig[8 * (size_t)j];
+            lr[kLightRec * j] = make_float4(l[0], l[1], l[2], l[3]);
+            lr[kLightRec * j + 1] = make_float4(l[4], l[5], l[6], c->h_lb_meta[2 * j + 1].x);
+            lr[kLightRec * j + 2] = c->h_lb_meta[2 * j];
+            lr[kLightRec * j + 3] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        HIP_TRY(c, hipMalloc(&c->d_lrec, lr.size() * sizeof(float4)));
+        HIP_TRY(c, hipMemcpy(c->d_lrec, lr.data(), lr.size() * sizeof(float4), hipMemcpyHostToDevice));
+    }
     c->n_surf = n;
     c->n_lights = nl;
     c->n_tri = cnt_tri;
@@ -2067,8 +2254,41 @@ static int launch_trace(rt_ctx* c, const KernelPick& kp, const TinyCam* T, bool 
         }
     }
     if (T) {
-        TinyCam Tv = *T;
-        void* args[] = {&S, &F, &Tv, &oa, &ob, &stats};
+        // the launch record (rt_cull.h TinyLaunch): the frame's, the scene's
+        // and the camera records' wave-uniform values, one argument
+        TinyLaunch Lr;
+        TinyHead& H = Lr.h;
+        H = TinyHead{};
+        std::memcpy(H.cam, F.cam, sizeof H.cam);
+        H.width = F.width;
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 3; ++j) H.orient[3 * i + j] = F.orient[4 * i + j];
+        H.half_w = F.half_w, H.half_h = F.half_h, H.inv_w = F.inv_w, H.inv_h = F.inv_h;
+        std::memcpy(H.bg, F.bg, sizeof H.bg);
+        H.height = F.height;
+        H.row_begin = F.row_begin, H.row_end = F.row_end;
+        H.band_rows = F.band_rows, H.band_count = F.band_count, H.band_index = F.band_index;
+        H.flags = F.flags;
+        H.n = T->n, H.masked = T->masked, H.mask = T->mask, H.tiles_x = T->tiles_x;
+        H.n_plane = S.n_plane;
+        // the planes' camera-ray constants, hit_plane's n . O + cst in float
+        // (this file is built without contraction, host and device)
+        const Vec3 O = make3(F.cam[0], F.cam[1], F.cam[2]);
+        for (int k = 0; k < kTinyPlanes && k < S.n_plane; ++k) {
+            const float* p = &c->h_plane[8 * (size_t)k];
+            H.plane[k] = make_float4(p[0], p[1], p[2], p[3]);
+            H.pnum[k] = dot(make3(p[0], p[1], p[2]), O) + p[3];
+            std::memcpy(&H.pidx[k], &p[4], sizeof(int));
+        }
+        H.rgba = oa, H.rgbf = ob, H.stats = stats;
+        H.geom = S.geom, H.mat = S.mat, H.lrec = c->d_lrec, H.planes = S.plane, H.quad = S.quad;
+        H.translucent = S.translucent;
+        H.lb_off = S.lb_off, H.lb_ent = S.lb_ent, H.lb_dcap = S.lb_dcap, H.cone_light = S.cone_light, H.tri = S.tri;
+        H.n_lights = S.n_lights, H.n_tri = S.n_tri, H.n_tri_opaque = S.n_tri_opaque;
+        H.n_plane_opaque = S.n_plane_opaque, H.n_quad = S.n_quad, H.n_quad_opaque = S.n_quad_opaque;
+        H.n_translucent = S.n_translucent, H.shadow_split = S.shadow_split;
+        std::memcpy(Lr.rec, T->rec, sizeof Lr.rec);
+        void* args[] = {&Lr};
         HIP_TRY(c, hipLaunchKernel(count ? tiny_kernel<true>(mode) : tiny_kernel<false>(mode), grid, block, args, 0, st));
         return RT_OK;
     }

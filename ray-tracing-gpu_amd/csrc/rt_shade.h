@@ -913,5 +913,206 @@ __device__ __forceinline__ Color shade_local(const SceneDev& S, const Mat& m, co
     return res;
 }
 
+// ---- the launch-camera kernels' light loop (rt_trace_tiny, rt_cull.h TinyHead)
+// Light-shade record, 64 bytes, one per light of the small-list light buffer
+// (built at upload, light_records): what shade_local's light-buffer loop
+// reads per light from lights[] and lb_meta[] — four loads behind three
+// waits — as one 16-dword scalar load.
+//   [x y z I] [r g b dcov] [off base, dcap base, n dcap, R (int bits)] [0 0 0 0]
+constexpr int kLightRec = 4;  // float4 per record
+
+// shadow_opaque_lb<false> (one light's shadow rays against the opaque
+// surfaces through the light's buffer) with the wave-uniform inputs where the
+// launch-camera kernel holds them: the slot's meta from the light's record,
+// the first kTinyPlanes opaque planes from the launch record (in SGPRs
+// across the lights: no load per light).  In the one-cell walk and the dcap
+// list an entry's 40 bytes are loaded together and the dmin / dcap gate is
+// applied to the loaded key: one round trip per entry instead of two.  The
+// gates' outcomes, the tests run and their order are shadow_opaque_lb's, so
+// the any-hit result is.
+__device__ __forceinline__ void shadow_opaque_tiny(const SceneDev& S, const TinyPlanes& PL, const float4 m0, float dcov,
+                                                   int l, const Vec3 P, const Vec3 L, float dist, bool& occ,
+                                                   Counters& cnt)
+{
+#pragma unroll
+    for (int k = 0; k < kTinyPlanes; ++k) {
+        if (k < S.n_plane_opaque) {
+            if (!__any(!occ)) return;
+            ++cnt.pla;
+            occ |= shadow_plane_hit(PL.a[k], P, L, dist);
+        }
+    }
+    for (int k = kTinyPlanes; k < S.n_plane_opaque; ++k) {
+        if (!__any(!occ)) return;
+        ++cnt.pla;
+        occ |= shadow_plane_hit(S.plane[2 * k], P, L, dist);
+    }
+    const float mx = fmaxf(fabsf(L.x), fmaxf(fabsf(L.y), fabsf(L.z)));
+    const bool cand = !occ & (mx >= 0.5f);  // a direction the lookup takes
+    const unsigned obase = __float_as_uint(m0.x), dbase = __float_as_uint(m0.y), ndcap = __float_as_uint(m0.z);
+    const int R = __float_as_int(m0.w);
+    const bool use = cand & !occ & (dist <= dcov) & (R > 0);
+    const int cell = use ? lb_cell(-L, R) : 0;
+    RT_MARK(cnt, 3);
+    // one cell for every lane that uses the buffer: its list by scalar loads
+    // (lb_slot); else each lane walks its own cell's list
+    const unsigned long long bu = __ballot(use);
+    const int cf = bu ? __builtin_amdgcn_readlane(cell, (int)__builtin_ctzll(bu)) : 0;
+    const bool one_cell = bu != 0 && __all(!use | (cell == cf));
+    unsigned e = 0, end = 0;
+    if (bu) {
+        if (one_cell) RT_EV(cnt, 0);
+        else RT_EV(cnt, 1);
+    }
+    if (one_cell) {
+        const unsigned* o = S.lb_off + obase + cf;
+        const unsigned q0 = o[0], q1 = o[1];
+        for (unsigned q = q0; q < q1; ++q) {
+            float4 c0, c1;
+            float2 c2;
+            lb_cell_entry(S.lb_ent, q, c0, c1, c2);
+            const bool act = use & !occ & (c0.w < dist);
+            if (!__any(act)) break;
+            ++cnt.tri;
+            RT_EV(cnt, 4);
+            if (act) {
+                const Vec3 e1 = make3(c1.x, c1.y, c1.z), e2 = make3(c1.w, c2.x, c2.y);
+                const TriU u = tri_u(make3(c0.x, c0.y, c0.z), e1, e2, P, L);
+                if (__any(u.ok)) {
+                    float t;
+                    const bool ok = tri_vt(u, e1, e2, L, t);
+                    occ |= ok & (t > kEps) & (t < dist);
+                }
+            }
+        }
+    } else if (use) {
+        const unsigned* o = S.lb_off + obase + cell;
+        e = o[0];
+        end = o[1];
+    }
+    bool have = e < end;
+    for (;;) {
+        const bool act = have & !occ;
+        if (!__any(act)) break;
+        RT_EV(cnt, 3);
+        bool go = false;
+        float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0;
+        float2 c2 = make_float2(0.f, 0.f);
+        if (act) {
+            lb_cell_entry(S.lb_ent, e, c0, c1, c2);
+            if (!(c0.w < dist)) {
+                have = false;  // this and every later entry lie beyond P (dmin)
+            } else {
+                go = true;
+                ++e;
+                have = e < end;
+            }
+        }
+        if (__any(go)) {
+            ++cnt.tri;
+            RT_EV(cnt, 4);
+            RT_EVN(cnt, 7, (unsigned)__popcll(__ballot(go)));
+            if (go) {
+                const Vec3 e1 = make3(c1.x, c1.y, c1.z), e2 = make3(c1.w, c2.x, c2.y);
+                const TriU u = tri_u(make3(c0.x, c0.y, c0.z), e1, e2, P, L);
+                if (__any(u.ok)) {
+                    float t;
+                    const bool ok = tri_vt(u, e1, e2, L, t);
+                    occ |= ok & (t > kEps) & (t < dist);
+                }
+            }
+        }
+    }
+    RT_MARK(cnt, 4);
+    // pairs not culled up to dcov, sorted by dcap (lb_slot)
+    for (unsigned q = 0; q < ndcap; ++q) {
+        float4 r0, r1;
+        float2 r2;
+        lb_cell_entry(S.lb_dcap, dbase + q, r0, r1, r2);
+        const bool need = use & !occ & (dist > r0.w);
+        if (!__any(need)) break;
+        ++cnt.tri;
+        RT_EV(cnt, 5);
+        if (need) {
+            const Vec3 e1 = make3(r1.x, r1.y, r1.z), e2 = make3(r1.w, r2.x, r2.y);
+            const TriU u = tri_u(make3(r0.x, r0.y, r0.z), e1, e2, P, L);
+            if (__any(u.ok)) {
+                float t;
+                const bool ok = tri_vt(u, e1, e2, L, t);
+                occ |= ok & (t > kEps) & (t < dist);
+            }
+        }
+    }
+    // lanes the buffer does not cover: every opaque triangle, culled per lane
+    if (__any(!occ & !use)) {
+        RT_EV(cnt, 6);
+        const float slack = dist * 1e-6f;
+        bool o2 = occ | use;
+        const float4* cone = S.cone_light + kConeRec * (size_t)S.n_tri * l;
+        for (int k = 0; k < S.n_tri_opaque; ++k) {
+            if (!__any(!o2)) break;
+            const float4 c0 = cone[2 * k], c1 = cone[2 * k + 1];
+            const bool reach = !o2 & light_reach(c0, c1, L, dist, slack);
+            if (!__any(reach)) continue;
+            const TriRec tr = load_tri(S, k);
+            ++cnt.tri;
+            const TriU r = tri_u(tr.p0, tr.e1, tr.e2, P, L);
+            if (!__any(r.ok && !o2)) continue;
+            float t;
+            const bool ok = tri_vt(r, tr.e1, tr.e2, L, t);
+            o2 |= ok & (t > kEps) & (t < dist);
+        }
+        occ = use ? occ : o2;
+    }
+    RT_MARK(cnt, 7);
+    for (int k = 0; k < S.n_quad_opaque; ++k) {
+        if (!__any(!occ)) break;
+        const float4* r = S.quad + 3 * k;
+        const float4 a = r[0], b = r[1], c = r[2];
+        float t;
+        ++cnt.qua;
+        const bool ok = hit_quadric(make_float4(0.f, a.x, a.y, a.z), make_float4(a.w, b.x, b.y, b.z),
+                                    make_float4(b.w, c.x, c.y, 0.f), P, L, t);
+        occ |= ok & (t > kEps) & (t < dist);
+    }
+}
+
+// shade_local's light-buffer loop (one light at a time, file order) for the
+// launch-camera kernels: the light's record is one load at the top of its
+// pass.  The host sends these kernels only scenes with shadow_split set (the
+// light buffer is built for no others).
+__device__ __forceinline__ Color shade_local_tiny(const SceneDev& S, const TinyPlanes& PL, const float4* lrec,
+                                                  const Mat& m, const Vec3 P, const Vec3 N, const Vec3 D,
+                                                  Counters& cnt, bool active)
+{
+    Color res = m.color * m.ka;
+    for (int li = 0; li < S.n_lights; ++li) {
+        const float4* r = lrec + kLightRec * li;
+        const float4 l0 = r[0], l1 = r[1], m0 = r[2];
+        const Vec3 Lr = make3(l0.x, l0.y, l0.z) - P;
+        const bool gate = active & (dot(Lr, N) > 0);  // Scene.cpp:1756, unnormalised
+        const float dist = sqrt_w(Lr.x * Lr.x + Lr.y * Lr.y + Lr.z * Lr.z);
+        const Vec3 L = Lr * recip_w(dist);
+        cnt.shadow += gate;
+        bool occ = !gate;
+        RT_MARK(cnt, 2);
+        shadow_opaque_tiny(S, PL, m0, l1.w, li, P, L, dist, occ, cnt);
+        RT_MARK(cnt, 7);
+        if (gate) {
+            Color F{0.0f, 0.0f, 0.0f};
+            if (!occ) {  // translucent surfaces, file order
+                F = Color{1.0f, 1.0f, 1.0f};
+                for (int q = 0; q < S.n_translucent; ++q) {
+                    Color fc;
+                    if (shadow_hit_record(S.geom + 4 * S.translucent[q], P, L, dist, fc, cnt)) F *= fc;
+                }
+            }
+            add_light(res, m, l0, l1, N, L, D, F);  // reads l1's colour only
+        }
+        RT_MARK(cnt, 5);
+    }
+    return res;
+}
+
 }  // namespace rt
 #endif  // RT_AMD_RT_SHADE_H
