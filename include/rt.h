@@ -218,6 +218,47 @@ int rt_create_cpu(int32_t threads, rt_ctx** out);
 int rt_cpu_render(rt_ctx*, const rt_frame*, uint8_t* rgba8_out);
 int rt_cpu_render_float(rt_ctx*, const rt_frame*, float* rgb_out);
 
+/* Supersampled anti-aliasing — an addition within ABI 8 (rt_abi_version()
+ * stays 8; test for RT_HAS_SUPERSAMPLE).  `samples` describes the SAMPLE
+ * grid: what rt_scene_set_resolution(s W, s H) + rt_scene_get_frame returns
+ * for a W x H image, its slab (row_begin / row_end) or band fields in sample
+ * rows.  The camera maps pixel px of a frame w wide to 2 px / w - 1, so the
+ * s x s samples of output pixel (x, y) are exactly pixels (s x + i, s y + j)
+ * of the plain frame at s W x s H.  With S that frame's float RGB, for s in
+ * 1..8 and per channel
+ *   out[y][x] = (((S[s y][s x] + S[s y][s x + 1]) + ...) + S[s y + s - 1][s x + s - 1]) / (float)(s s)
+ * — sample rows bottom row first, left to right within a row, a sequential
+ * float32 sum that starts as the first sample, then one IEEE division; RGBA8
+ * is rt_render's unorm8 of that float; s = 1 is the plain render's bits.  The
+ * output has width / s columns and rt_ss_rows(samples, s) rows (the sample
+ * frame's rows / s), row 0 = bottom, packed by the slab / band rules (a band
+ * row past the frame stays unwritten, as in rt_render).
+ * RT_E_ARG, nothing enqueued: s outside 1..8; s does not divide width or
+ * height, or (slabs) row_begin or row_end; band_rows > 0 not a multiple of
+ * 16 s.
+ * The samples are rendered by the plain render's kernels into a float
+ * intermediate owned by the context and resolved on the same stream by
+ * rt_resolve_kernel (csrc/rt_resolve.h).  Slab frames that do not render as
+ * a wavefront are rendered and resolved in row chunks (RT_OPT_SS_CHUNK_ROWS),
+ * which bounds the intermediate.  The intermediate is shared by the context's
+ * streams: calls on different streams are ordered against each other by
+ * events (no host sync needed), and it is allocated only when it grows.
+ * Inside a hipGraph capture it cannot grow: RT_E_STATE unless an earlier
+ * uncaptured call sized it (and, as for rt_render_async, the camera state is
+ * current).  rt_stats of a synchronous call: kernel_ms covers trace and
+ * resolve, primary_rays counts samples.  The rt_cpu_* pair is the CPU
+ * backend's (same arithmetic, one shared function); each backend's calls
+ * return RT_E_STATE on the other's context. */
+#define RT_HAS_SUPERSAMPLE 1
+int rt_render_ss(rt_ctx*, const rt_frame* samples, int32_t s, uint8_t* rgba8_out);   /* sync, host or device ptr */
+int rt_render_ss_float(rt_ctx*, const rt_frame* samples, int32_t s, float* rgb_out); /* sync, host or device ptr */
+int rt_render_ss_async(rt_ctx*, const rt_frame* samples, int32_t s, uint8_t* rgba8_dev, float* rgb_dev,
+                       void* hip_stream);                                            /* either may be NULL */
+int rt_cpu_render_ss(rt_ctx*, const rt_frame* samples, int32_t s, uint8_t* rgba8_out);
+int rt_cpu_render_ss_float(rt_ctx*, const rt_frame* samples, int32_t s, float* rgb_out);
+/* Output rows of a supersampled render; -1 if the (frame, s) pair is invalid. */
+int32_t rt_ss_rows(const rt_frame* samples, int32_t s);
+
 /* ABI 4: context options.  A/B and test switches and tuning knobs; no option
  * changes a single bit of any image.  Upload options take effect at the next
  * rt_upload_scene, launch options at the next render.                      */
@@ -298,6 +339,14 @@ enum {
        removed in ABI 6: rt_set_option returns RT_E_ARG for them.  Their code
        and measurements: profiles/r04/set_aside/. */
 };
+/* Added within ABI 8 with the supersampled renders (a macro, not an
+ * enumerator: the enum above is ABI 8's option list as released).  Launch:
+ * output rows per chunk of rt_render_ss* on slab frames that do not render
+ * as a wavefront, rounded up to a multiple of 16 (a chunk is then a multiple
+ * of 16 s sample rows); 0 (default) = auto: the fewest equal chunks whose
+ * float samples stay within 224 MiB each (one chunk up to 3840 x 2160
+ * samples and beyond; two at 7680 x 4320).  Never changes an image. */
+#define RT_OPT_SS_CHUNK_ROWS 20
 int rt_set_option(rt_ctx*, int32_t option, double value);
 int rt_get_option(rt_ctx*, int32_t option, double* value);
 /* ABI 4, upload: the far light-buffer ladder of big lists — rising distance

@@ -83,6 +83,13 @@ int rt_debug_bvh_rays_wave(rt_ctx*, const float* rays, int n, int* out_idx, floa
  * `blocks` workgroups on `device`; *failures = lanes that disagreed. */
 int rt_debug_selftest(int device, int blocks, unsigned* failures);
 
+/* The supersampling resolve alone (csrc/rt_resolve.h, tools/ssaa_probe.py):
+ * rows_out rows of width / s pixels from the s rows_out x width float RGB
+ * samples at samples_dev, enqueued on hip_stream; device pointers, either
+ * output may be NULL; s in 2..8 dividing width. */
+int rt_debug_resolve(rt_ctx*, const float* samples_dev, int width, int s, int rows_out, float* rgb_dev,
+                     unsigned* rgba_dev, void* hip_stream);
+
 #ifdef RT_PROF
 /* Only in a library built with -DRT_PROF (tools/prof_sections.py,
  * tools/prof_tiles.py): per-section shader-clock totals and event counts

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "rt_math.h"
+#include "rt_resolve.h"
 
 #pragma clang fp contract(off)
 
@@ -385,6 +386,29 @@ int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uin
     for (auto& t : pool) t.join();
     if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return RT_OK;
+}
+
+void cpu_resolve(const float* samples, int width, int s, int rows_out, uint8_t* rgba, float* rgb, double* ms)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const int wo = width / s;
+    const size_t pitch = (size_t)width * 3;
+    for (int q = 0; q < rows_out; ++q) {
+        for (int x = 0; x < wo; ++x) {
+            const Color c = resolve_px(samples + (size_t)q * s * pitch + (size_t)x * s * 3, pitch, s);
+            const size_t o = (size_t)q * wo + x;
+            if (rgb) {
+                rgb[3 * o] = c.r;
+                rgb[3 * o + 1] = c.g;
+                rgb[3 * o + 2] = c.b;
+            }
+            if (rgba) {
+                const unsigned px8 = resolve_rgba8(c);
+                std::memcpy(rgba + 4 * o, &px8, 4);
+            }
+        }
+    }
+    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace rt

@@ -12,6 +12,10 @@ void cpu_free(void* handle);
 // Render `rows` output rows of frame f (slab or band set) on `threads` host
 // threads (<= 0: all); either output may be null.  *ms = wall time.
 int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uint8_t* rgba8, float* rgb, double* ms);
+// The supersampling resolve (rt_resolve.h resolve_px, the HIP kernel's own
+// arithmetic): rows_out rows of width / s pixels from their packed sample
+// rows; either output may be null.  *ms = wall time.
+void cpu_resolve(const float* samples, int width, int s, int rows_out, uint8_t* rgba8, float* rgb, double* ms);
 }  // namespace rt
 
 #endif  // RT_AMD_RT_CPU_HPP

@@ -44,6 +44,7 @@
 #include "rt_shade.h"
 #include "rt_bvh.h"
 #include "rt_wavefront.h"
+#include "rt_resolve.h"
 
 #pragma clang fp contract(off)
 
@@ -967,6 +968,17 @@ struct rt_ctx {
         hipStream_t last = nullptr;
         bool pending = false;
     } wf;
+    // Supersampled renders (rt_render_ss*): the float sample intermediate,
+    // one per context, grown on demand: a call on another stream than the
+    // last one's waits for that call's resolve (ev) before it overwrites it.
+    struct SsBuf {
+        float* mem = nullptr;
+        size_t bytes = 0;
+        hipEvent_t ev = nullptr;  // after the last resolve
+        hipStream_t last = nullptr;
+        bool pending = false;
+    } ss;
+    double opt_ss_chunk_rows = 0.0;  // RT_OPT_SS_CHUNK_ROWS (0 = auto)
     int opt_wavefront = 1;      // RT_OPT_WAVEFRONT
     int opt_wf_sort = 1;        // RT_OPT_WF_SORT
     bool opt_wf_overlap = true; // RT_OPT_WF_OVERLAP
@@ -1092,6 +1104,7 @@ static int sync_all(rt_ctx* c)
     c->state_pending = false;
     c->state_stream = nullptr;
     c->wf.pending = false;
+    c->ss.pending = false;
     free_deferred(c);
     return RT_OK;
 }
@@ -1166,6 +1179,10 @@ RT_EXPORT int rt_set_option(rt_ctx* c, int32_t opt, double v)
         if (v < 0 || v > 4096 || v != std::floor(v)) return RT_E_ARG;
         c->opt_xcd_stripe = (int)v;
         return RT_OK;
+    case RT_OPT_SS_CHUNK_ROWS:
+        if (v < 0 || v > 1e9 || v != std::floor(v)) return RT_E_ARG;
+        c->opt_ss_chunk_rows = v;
+        return RT_OK;
     case RT_OPT_CB_CAPACITY:
         if (v < 0 || v > 4e9 || v != std::floor(v)) return RT_E_ARG;
         if (v != c->opt_cb_capacity) c->cb.valid = false;
@@ -1195,6 +1212,7 @@ RT_EXPORT int rt_get_option(rt_ctx* c, int32_t opt, double* v)
     case RT_OPT_XCD_DEAL: *v = c->opt_xcd_deal; return RT_OK;
     case RT_OPT_XCD_STRIPE: *v = c->opt_xcd_stripe; return RT_OK;
     case RT_OPT_LB_UNROLL: *v = c->opt_lb_unroll ? 1 : 0; return RT_OK;
+    case RT_OPT_SS_CHUNK_ROWS: *v = c->opt_ss_chunk_rows; return RT_OK;
     default: return RT_E_ARG;
     }
 }
@@ -1275,6 +1293,8 @@ RT_EXPORT void rt_destroy(rt_ctx* c)
     hipFree(c->wf.hist);
     hipFree(c->wf.bsum);
     hipFree(c->d_skey);
+    hipFree(c->ss.mem);
+    if (c->ss.ev) hipEventDestroy(c->ss.ev);
     if (c->wf.ev) hipEventDestroy(c->wf.ev);
     if (c->wf.ev_t) hipEventDestroy(c->wf.ev_t);
     if (c->wf.ev_s) hipEventDestroy(c->wf.ev_s);
@@ -2829,8 +2849,91 @@ static int wf_levels(rt_ctx* c, const SceneDev& S, const FrameDev& F, int levels
     return RT_OK;
 }
 
+// ---- supersampled renders (rt.h rt_render_ss*, rt_resolve.h)
+// Output rows of (frame, s); -1 if the pair is invalid.
+static int ss_rows_of(const rt_frame* f, int s)
+{
+    if (!f || s < 1 || s > kSsMax || !frame_ok(f)) return -1;
+    if (f->width % s != 0 || f->height % s != 0) return -1;
+    if (f->band_rows != 0) {
+        if (f->band_rows % (16 * s) != 0) return -1;
+    } else if (f->row_begin % s != 0 || f->row_end % s != 0) {
+        return -1;
+    }
+    return frame_rows(f) / s;
+}
+
+// The sample rows a render of f writes, of its `rows` packed rows: all of a
+// slab; of a band set the rows inside the frame (only the frame's last band
+// can reach past it, and it is the last of its rank's packed bands).
+static int ss_valid_rows(const rt_frame* f, int rows)
+{
+    if (f->band_rows == 0) return rows;
+    int v = 0;
+    for (int b = 0; b < rows / f->band_rows; ++b) {
+        const long long y0 = ((long long)b * f->band_count + f->band_index) * f->band_rows;
+        v += (int)std::max(0LL, std::min<long long>(f->band_rows, f->height - y0));
+    }
+    return v;
+}
+
+// Sample rows per chunk of a supersampled slab frame (RT_OPT_SS_CHUNK_ROWS
+// output rows, a multiple of 16, times s; so every chunk starts on a multiple
+// of 16 s sample rows of the slab: the 8-row tiles of the camera buffer stay
+// aligned).  Auto: the fewest equal chunks whose float samples stay within
+// 224 MiB each — under the 256 MiB Infinity Cache, so the resolve still finds
+// them there.  Measured (tools/ssaa_probe.py): every chunk more
+// costs 12 us (C2) to 50 us (C3) of drained GPU at 3840 x 2160 samples, where
+// one chunk (95 MiB) is fastest; at 7680 x 4320 (380 MiB) two chunks beat one
+// by 1.4% and four lose 2.4%.
+static int ss_chunk_sample_rows(const rt_ctx* c, const rt_frame* f, int rows, int s)
+{
+    const double row_bytes = (double)f->width * 12.0;
+    double ch = c->opt_ss_chunk_rows;
+    if (ch == 0) {
+        const double n = std::ceil(row_bytes * rows / (224.0 * 1048576.0));
+        if (n <= 1) return rows;
+        ch = std::ceil((double)(rows / s) / n);
+    }
+    ch = std::max(16.0, std::ceil(ch / 16.0) * 16.0);
+    return (int)std::min((double)rows, ch * s);
+}
+
+template <int S>
+static const void* resolve_kernel(bool vec)
+{
+    return vec ? (const void*)&rt_resolve_kernel<S, true> : (const void*)&rt_resolve_kernel<S, false>;
+}
+
+// rows_out output rows of width / s pixels from their s rows_out packed
+// sample rows at `samples`, on st.
+static int launch_resolve(rt_ctx* c, const float* samples, int width, int s, int rows_out, float* rgb, unsigned* rgba,
+                          hipStream_t st)
+{
+    if (rows_out <= 0) return RT_OK;
+    int wo = width / s;
+    const bool vec = width % 4 == 0 && ((uintptr_t)samples & 15) == 0;
+    const void* k = nullptr;
+    switch (s) {
+    case 2: k = resolve_kernel<2>(vec); break;
+    case 3: k = resolve_kernel<3>(vec); break;
+    case 4: k = resolve_kernel<4>(vec); break;
+    case 5: k = resolve_kernel<5>(vec); break;
+    case 6: k = resolve_kernel<6>(vec); break;
+    case 7: k = resolve_kernel<7>(vec); break;
+    case 8: k = resolve_kernel<8>(vec); break;
+    default: c->err = "no resolve kernel for this factor"; return RT_E_ARG;
+    }
+    const size_t lanes = (size_t)(wo / (vec ? resolve_run(s) : 1)) * (size_t)rows_out;
+    void* args[] = {&samples, &width, &wo, &rows_out, &rgb, &rgba};
+    HIP_TRY(c, hipLaunchKernel(k, dim3((unsigned)((lanes + 255) / 256)), dim3(256), args, 0, st));
+    return RT_OK;
+}
+
+// ss > 1: a supersampled render — rgba_dev / rgb_dev take the resolved
+// width / ss x rows / ss image (no host_out); the samples go to c->ss.
 static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_dev, hipStream_t st, bool timed,
-                  bool sync_path, void* host_out = nullptr)
+                  bool sync_path, void* host_out = nullptr, int ss = 1)
 {
     if (!c || !f) return RT_E_ARG;
     if (!c->uploaded) {
@@ -2875,6 +2978,27 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
         bool ok = false;
         if (int rc = wf_ensure(c, f, rows, depth, capturing, &ok)) return rc;
         wf = ok;
+    }
+    // A supersampled frame's samples: slabs that are not wavefronts in row
+    // chunks (the intermediate holds one chunk), everything else whole.
+    int ss_step = rows;
+    if (ss > 1 && rows > 0) {
+        if (!wf && f->band_rows == 0) ss_step = ss_chunk_sample_rows(c, f, rows, ss);
+        rt_ctx::SsBuf& B = c->ss;
+        const size_t need = (size_t)ss_step * f->width * 12;
+        if (need > B.bytes) {
+            if (capturing) {
+                c->err = "rt_render_ss_async in a capture: the sample intermediate is not sized (render the frame "
+                         "once outside the capture)";
+                return RT_E_STATE;
+            }
+            free_later(c, B.mem);  // an enqueued resolve may still read the old one
+            B.mem = nullptr;
+            B.bytes = 0;
+            HIP_TRY(c, hipMalloc((void**)&B.mem, need));
+            B.bytes = need;
+        }
+        if (!B.ev) HIP_TRY(c, hipEventCreateWithFlags(&B.ev, hipEventDisableTiming));
     }
     const bool count = (f->flags & RT_FLAG_STATS) != 0;
     const bool small = (double)f->width * rows < 4e6 && c->opt_lb_unroll;
@@ -2921,7 +3045,40 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
         if (W.sort)  // the bin counts (level 1's: the level-0 kernel's appends)
             HIP_TRY(c, hipMemsetAsync(W.dev.hist, 0, 2 * W.hcap * sizeof(unsigned), st));
     }
-    if (nch <= 1) {
+    if (ss > 1) {
+        rt_ctx::SsBuf& B = c->ss;
+        if (B.pending && B.last != st && !capturing) HIP_TRY(c, hipStreamWaitEvent(st, B.ev, 0));
+        const int wo = f->width / ss;
+        const int vrows = ss_valid_rows(f, rows);
+        for (int r0 = 0; r0 < rows; r0 += ss_step) {
+            const int r1 = std::min(rows, r0 + ss_step);
+            FrameDev Fc = F;
+            if (ss_step < rows) {
+                Fc.row_begin = f->row_begin + r0;
+                Fc.row_end = f->row_begin + r1;
+            }
+            if (int rc = launch_trace(c, kp, tiny, f->flags & RT_FLAG_STATS, S, Fc, f->width, r1 - r0, nullptr, B.mem,
+                                      stats, st, tmode))
+                return rc;
+            if (wf) {  // (one chunk)
+                if (int rc = wf_levels(c, S, Fc, depth, count, nullptr, B.mem, stats, st)) return rc;
+                HIP_TRY(c, hipEventRecord(c->wf.ev, st));
+                c->wf.last = st;
+                c->wf.pending = true;
+            }
+            const int q0 = r0 / ss, nq = (std::max(r0, std::min(r1, vrows)) - r0) / ss;
+            if (int rc = launch_resolve(c, B.mem, f->width, ss, nq, rgb_dev ? rgb_dev + (size_t)q0 * wo * 3 : nullptr,
+                                        rgba_dev ? rgba_dev + (size_t)q0 * wo : nullptr, st))
+                return rc;
+        }
+        if (tmode == 2)
+            if (int rc = tiny_masks_stored(c, st)) return rc;
+        if (!capturing) {
+            HIP_TRY(c, hipEventRecord(B.ev, st));
+            B.last = st;
+            B.pending = true;
+        }
+    } else if (nch <= 1) {
         if (int rc = launch_trace(c, kp, tiny, f->flags & RT_FLAG_STATS, S, F, f->width, rows, rgba_dev, rgb_dev, stats,
                                   st, tmode))
             return rc;
@@ -2986,6 +3143,7 @@ static int finish_sync(rt_ctx* c, const rt_frame* f, hipStream_t st, bool timed)
     c->state_pending = false;
     c->state_stream = nullptr;
     c->wf.pending = false;
+    c->ss.pending = false;
     free_deferred(c);
     if (timed) {
         float ms = 0.f;
@@ -3210,6 +3368,7 @@ RT_EXPORT int rt_prepare_camera(rt_ctx* c, const rt_frame* f)
     c->state_pending = false;
     c->state_stream = nullptr;
     c->wf.pending = false;
+    c->ss.pending = false;
     free_deferred(c);
     return RT_OK;
 }
@@ -3244,6 +3403,107 @@ RT_EXPORT int rt_cpu_render(rt_ctx* c, const rt_frame* f, uint8_t* rgba8_out)
 RT_EXPORT int rt_cpu_render_float(rt_ctx* c, const rt_frame* f, float* rgb_out)
 {
     return cpu_render_sync(c, f, nullptr, rgb_out);
+}
+
+// ---- supersampled renders (rt.h)
+RT_EXPORT int32_t rt_ss_rows(const rt_frame* f, int32_t s) { return ss_rows_of(f, s); }
+
+static int ss_check(rt_ctx* c, const rt_frame* f, int s)
+{
+    if (ss_rows_of(f, s) >= 0) return RT_OK;
+    c->err = "bad supersampling: s in 1..8 must divide the sample frame's width, height and slab rows "
+             "(band_rows: a multiple of 16 s)";
+    return RT_E_ARG;
+}
+
+static int render_ss_sync(rt_ctx* c, const rt_frame* f, int s, void* out, bool as_float)
+{
+    if (!c || !f || !out) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    if (int rc = ss_check(c, f, s)) return rc;
+    if (s == 1) return render_sync(c, f, out, as_float);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = fence_async(c, c->stream)) return rc;
+    if (int rc = wait_state(c, c->stream)) return rc;
+    const size_t px = (size_t)(f->width / s) * (size_t)ss_rows_of(f, s);
+    const size_t bytes = px * (as_float ? 12 : 4);
+    const bool dev = is_device_ptr(out);
+    void* target = out;
+    if (!dev) {
+        if (int rc = ensure_scratch(c, std::max<size_t>(bytes, 16))) return rc;
+        target = c->d_scratch;
+    }
+    if (int rc = launch(c, f, as_float ? nullptr : (unsigned*)target, as_float ? (float*)target : nullptr, c->stream,
+                        true, true, nullptr, s))
+        return rc;
+    // (a band set's rows past the frame are not written: they are not copied either)
+    const size_t wrote = (size_t)(f->width / s) * (size_t)(ss_valid_rows(f, frame_rows(f)) / s) * (as_float ? 12 : 4);
+    if (!dev && wrote) HIP_TRY(c, hipMemcpyAsync(out, target, wrote, hipMemcpyDeviceToHost, c->stream));
+    return finish_sync(c, f, c->stream, true);
+}
+
+RT_EXPORT int rt_render_ss(rt_ctx* c, const rt_frame* f, int32_t s, uint8_t* rgba8_out)
+{
+    return render_ss_sync(c, f, s, rgba8_out, false);
+}
+
+RT_EXPORT int rt_render_ss_float(rt_ctx* c, const rt_frame* f, int32_t s, float* rgb_out)
+{
+    return render_ss_sync(c, f, s, rgb_out, true);
+}
+
+RT_EXPORT int rt_render_ss_async(rt_ctx* c, const rt_frame* f, int32_t s, uint8_t* rgba8_dev, float* rgb_dev,
+                                 void* stream)
+{
+    if (!c || !f) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    if (int rc = ss_check(c, f, s)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return launch(c, f, (unsigned*)rgba8_dev, rgb_dev, (hipStream_t)stream, false, false, nullptr, s);
+}
+
+static int cpu_render_ss_sync(rt_ctx* c, const rt_frame* f, int s, uint8_t* rgba, float* rgb)
+{
+    if (!c || !f || (!rgba && !rgb)) return RT_E_ARG;
+    if (!c->cpu) {
+        c->err = "rt_cpu_render_ss needs a CPU context (rt_create_cpu)";
+        return RT_E_STATE;
+    }
+    if (int rc = ss_check(c, f, s)) return rc;
+    if (s == 1) return cpu_render_sync(c, f, rgba, rgb);
+    if (!c->uploaded) {
+        c->err = "render before rt_upload_scene";
+        return RT_E_STATE;
+    }
+    c->last = rt_stats{};
+    const int rows = frame_rows(f);
+    std::vector<float> samples((size_t)rows * f->width * 3);
+    double ms = 0.0, ms2 = 0.0;
+    if (int rc = cpu_render(c->cpu_scene, c->cpu_threads, f, rows, nullptr, samples.data(), &ms)) return rc;
+    cpu_resolve(samples.data(), f->width, s, ss_valid_rows(f, rows) / s, rgba, rgb, &ms2);
+    c->last.kernel_ms = (float)(ms + ms2);
+    return RT_OK;
+}
+
+RT_EXPORT int rt_cpu_render_ss(rt_ctx* c, const rt_frame* f, int32_t s, uint8_t* rgba8_out)
+{
+    return cpu_render_ss_sync(c, f, s, rgba8_out, nullptr);
+}
+
+RT_EXPORT int rt_cpu_render_ss_float(rt_ctx* c, const rt_frame* f, int32_t s, float* rgb_out)
+{
+    return cpu_render_ss_sync(c, f, s, nullptr, rgb_out);
+}
+
+// Diagnostic (include/rt_debug.h): the resolve kernel alone.
+RT_EXPORT int rt_debug_resolve(rt_ctx* c, const float* samples, int width, int s, int rows_out, float* rgb,
+                               unsigned* rgba, void* stream)
+{
+    if (!c || !samples || (!rgb && !rgba) || s < 2 || s > kSsMax || width <= 0 || width % s != 0 || rows_out < 0)
+        return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return launch_resolve(c, samples, width, s, rows_out, rgb, rgba, (hipStream_t)stream);
 }
 
 RT_EXPORT int rt_last_stats(rt_ctx* c, rt_stats* out)

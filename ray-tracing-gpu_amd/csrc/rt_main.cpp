@@ -3,6 +3,7 @@
 //   rt_render <scene.dat> [-x W] [-y H] [-d depth] [-o out.ppm] [-g gpus]
 //             [--device first] [--bands] [-n frames] [-s]
 //             [--gather rccl|host] [--backend hip|cpu] [--threads N]
+//             [--ssaa N]
 //
 // Kept from Main.cpp:51-199: argv[1] is the scene file, -x / -y set the
 // resolution (default 512x256, Var.cpp:4-5), the same [ETAT]/[ERREUR] log
@@ -30,7 +31,9 @@
 // memory — the same partition, without a collective.  --backend cpu renders
 // on host threads instead (rt_create_cpu,
 // the reference's CPU branch, chosen there by CVar::g_ComputerShadersON):
-// the same image, the GPU never touched.
+// the same image, the GPU never touched.  --ssaa N (1..8) writes the W x H
+// image resolved from N x N samples per pixel (rt_render_ss / rt_cpu_render_ss:
+// the scene is prepared at N W x N H), on either backend, one GPU.
 #include <hip/hip_runtime_api.h>
 
 #include <dlfcn.h>
@@ -296,7 +299,7 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "[ERREUR]: Aucune fichier de scene ne fut passe en argument !\n");
         return 1;
     }
-    int W = 512, H = 256, depth = 0, dev0 = 0, frames = 1, gpus = 1, threads = 0;
+    int W = 512, H = 256, depth = 0, dev0 = 0, frames = 1, gpus = 1, threads = 0, ssaa = 1;
     bool stats = false, bands = false, cpu = false, dev_given = false, g_given = false;
     int gather = -1;  // -1 auto (RCCL for -g > 1 on distinct GPUs), 0 host, 1 RCCL
     const char* out = nullptr;
@@ -312,6 +315,11 @@ int main(int argc, char** argv)
         }
         if (std::strcmp(argv[i], "--bands") == 0) {
             bands = true;
+            continue;
+        }
+        if (std::strcmp(argv[i], "--ssaa") == 0) {
+            ssaa = 0;
+            next(ssaa);
             continue;
         }
         if (std::strcmp(argv[i], "--threads") == 0) {
@@ -355,6 +363,10 @@ int main(int argc, char** argv)
     // -g was the HIP device index before ABI 3; it is now the GPU count
     if (g_given && !dev_given)
         std::fprintf(stderr, "[NOTE]: -g %d = number of GPUs (from device 0); the device index is --device\n", gpus);
+    if (ssaa < 1 || ssaa > 8) return fail("arguments", RT_E_ARG, "--ssaa is 1..8");
+    if (ssaa > 1 && (gpus != 1 || bands || gather == 1))
+        return fail("arguments", RT_E_ARG,
+                    "--ssaa renders on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
     if (((W - 1) & W) || ((H - 1) & H))
         std::fprintf(stderr, "[ATTENTION]: Resolution %dx%d n'est pas une puissance de deux "
                              "(accepted: the render core has no such restriction)\n", W, H);
@@ -362,7 +374,7 @@ int main(int argc, char** argv)
     rt_scene* scene = nullptr;
     int rc = rt_scene_create(&scene);
     if (rc) return fail("rt_scene_create", rc, "");
-    rt_scene_set_resolution(scene, W, H);
+    rt_scene_set_resolution(scene, W * ssaa, H * ssaa);  // (--ssaa: the sample grid)
     rt_scene_set_max_bounces(scene, depth);
     std::printf("[ETAT]: Traitement du fichier de donnees de la scene...\n");
     if ((rc = rt_scene_load_file(scene, argv[1]))) return fail("TraiterFichierDeScene", rc, rt_scene_error(scene));
@@ -383,7 +395,8 @@ int main(int argc, char** argv)
         double total = 0.0;
         for (int k = 0; k < frames; ++k) {
             const auto t0 = std::chrono::steady_clock::now();
-            if ((rc = rt_cpu_render(c, &frame, img.data()))) return fail("LancerRayons", rc, rt_last_error(c));
+            if ((rc = ssaa > 1 ? rt_cpu_render_ss(c, &frame, ssaa, img.data()) : rt_cpu_render(c, &frame, img.data())))
+                return fail("LancerRayons", rc, rt_last_error(c));
             total += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
         std::printf("[ETAT]: Termine! --> Temps total de rendu : %.6f secondes (%d frame(s), CPU)\n", total, frames);
@@ -396,6 +409,24 @@ int main(int argc, char** argv)
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("rt_create", RT_E_HIP, "no HIP device");
     // one context per GPU share; part r = rows of slab r, or band set r
     const int band = bands ? 16 : 0;
+    if (ssaa > 1) {  // one context, the sample frame resolved on the device
+        rt_ctx* c = nullptr;
+        if ((rc = rt_create(dev0 % ndev, &c))) return fail("rt_create", rc, c ? rt_last_error(c) : "");
+        if ((rc = rt_upload_scene(c, &flat))) return fail("rt_upload_scene", rc, rt_last_error(c));
+        std::vector<uint8_t> img((size_t)W * H * 4);
+        std::printf("[ETAT]: Lancer de rayons (%d x %d echantillons par pixel)...\n", ssaa, ssaa);
+        double total = 0.0;
+        for (int k = 0; k < frames; ++k) {
+            const auto t0 = std::chrono::steady_clock::now();
+            if ((rc = rt_render_ss(c, &frame, ssaa, img.data()))) return fail("LancerRayons", rc, rt_last_error(c));
+            total += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        print_done(c, total, frames, 1, 0, stats);
+        if (out && write_ppm(out, W, H, img)) return fail("fopen", -1, out);
+        rt_destroy(c);
+        rt_scene_destroy(scene);
+        return 0;
+    }
     std::vector<rt_ctx*> ctx((size_t)gpus, nullptr);
     std::vector<rt_frame> part((size_t)gpus, frame);
     std::vector<std::vector<uint8_t>> img((size_t)gpus);

@@ -24,7 +24,7 @@ import numpy as np
 
 __all__ = [
     "RtError", "SceneFlat", "Frame", "Stats", "Scene", "Context", "CpuContext", "CScene", "lib", "band_rows",
-    "frame_rows",
+    "frame_rows", "ss_rows", "SS_OPTIONS",
     "LIB_PATH", "TRIANGLE", "PLANE", "QUADRIC", "FLAG_STATS", "OPTIONS", "camera_path",
 ]
 
@@ -37,6 +37,8 @@ FLAG_STATS = 1
 OPTIONS = {"light_buffer": 1, "camera_buffer": 2, "union_pretest": 3, "lb_scale": 4, "dcov_near": 5,
            "cb_inline_max_mb": 6, "host_chunk_mb": 7, "cb_capacity": 8, "launch_camera": 12, "bvh": 13, "wavefront": 14,
            "wf_sort": 15, "xcd_deal": 16, "xcd_stripe": 17, "lb_unroll": 18, "wf_overlap": 19}
+# rt.h's additions within ABI 8 (macros beside the RT_OPT_* enum): set_option / get_option take these names too
+SS_OPTIONS = {"ss_chunk_rows": 20}
 _ERRORS = {-1: "RT_E_ARG", -2: "RT_E_IO", -3: "RT_E_PARSE", -4: "RT_E_STATE", -5: "RT_E_HIP",
            -6: "RT_E_UNSUPPORTED"}
 
@@ -107,6 +109,12 @@ SIGNATURES = {
     "rt_create_cpu": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_VP)]),
     "rt_cpu_render": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
     "rt_cpu_render_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
+    "rt_render_ss": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.c_int32, _VP]),
+    "rt_render_ss_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.c_int32, _VP]),
+    "rt_render_ss_async": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.c_int32, _VP, _VP, _VP]),
+    "rt_cpu_render_ss": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.c_int32, _VP]),
+    "rt_cpu_render_ss_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.c_int32, _VP]),
+    "rt_ss_rows": (ctypes.c_int32, [ctypes.POINTER(Frame), ctypes.c_int32]),
     "rt_upload_scene": (ctypes.c_int, [_VP, ctypes.POINTER(SceneFlat)]),
     "rt_render": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
     "rt_render_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
@@ -137,6 +145,22 @@ def frame_rows(frame: "Frame") -> int:
     if frame.band_rows:  # an invalid layout gives 0 rows here; the render call rejects it
         return max(0, lib().rt_band_rows(frame.height, frame.band_rows, frame.band_count, frame.band_index))
     return frame.row_end - frame.row_begin
+
+
+def ss_rows(frame: "Frame", s: int) -> int:
+    """Rows a supersampled render of the sample frame `frame` with factor `s`
+    writes (rt.h rt_ss_rows); ValueError if the pair is invalid."""
+    rows = lib().rt_ss_rows(ctypes.byref(frame), int(s))
+    if rows < 0:
+        raise ValueError("bad supersampling: s in 1..8 must divide the sample frame's width, height and slab rows "
+                         "(band_rows: a multiple of 16 s)")
+    return rows
+
+
+def _option(name) -> int:
+    if isinstance(name, str):
+        return OPTIONS[name] if name in OPTIONS else SS_OPTIONS[name]
+    return int(name)
 
 
 def lib() -> ctypes.CDLL:
@@ -232,12 +256,12 @@ class Context:
                 self.set_option(k, v)
 
     def set_option(self, name, value: float):
-        """rt_set_option: `name` is a key of OPTIONS (or the RT_OPT_* number)."""
-        opt = OPTIONS[name] if isinstance(name, str) else int(name)
+        """rt_set_option: `name` is a key of OPTIONS or SS_OPTIONS (or the RT_OPT_* number)."""
+        opt = _option(name)
         _check("rt_set_option", lib().rt_set_option(self._h, opt, float(value)), self._err)
 
     def get_option(self, name) -> float:
-        opt = OPTIONS[name] if isinstance(name, str) else int(name)
+        opt = _option(name)
         v = ctypes.c_double()
         _check("rt_get_option", lib().rt_get_option(self._h, opt, ctypes.byref(v)), self._err)
         return v.value
@@ -287,6 +311,24 @@ class Context:
     def render_async(self, frame: Frame, rgba_dev_ptr: int = 0, rgb_dev_ptr: int = 0, stream: int = 0):
         _check("rt_render_async", lib().rt_render_async(self._h, ctypes.byref(frame), rgba_dev_ptr or None,
                                                         rgb_dev_ptr or None, stream or None), self._err)
+
+    def render_ss(self, frame: Frame, s: int) -> np.ndarray:
+        """rt_render_ss: `frame` is the SAMPLE frame (s W x s H); returns the
+        resolved RGBA8 (ss_rows(frame, s), frame.width / s, 4), row 0 = bottom."""
+        out = np.zeros((ss_rows(frame, s), frame.width // s, 4), np.uint8)
+        _check("rt_render_ss", lib().rt_render_ss(self._h, ctypes.byref(frame), s, out.ctypes.data), self._err)
+        return out
+
+    def render_ss_float(self, frame: Frame, s: int) -> np.ndarray:
+        out = np.zeros((ss_rows(frame, s), frame.width // s, 3), np.float32)
+        _check("rt_render_ss_float", lib().rt_render_ss_float(self._h, ctypes.byref(frame), s, out.ctypes.data),
+               self._err)
+        return out
+
+    def render_ss_async(self, frame: Frame, s: int, rgba_dev_ptr: int = 0, rgb_dev_ptr: int = 0, stream: int = 0):
+        """rt_render_ss_async: device pointers to the resolved image, enqueued on `stream`."""
+        _check("rt_render_ss_async", lib().rt_render_ss_async(self._h, ctypes.byref(frame), s, rgba_dev_ptr or None,
+                                                              rgb_dev_ptr or None, stream or None), self._err)
 
     def stats(self) -> Stats:
         s = Stats()
@@ -353,6 +395,19 @@ class CpuContext:
                self._err)
         return out
 
+    def render_ss(self, frame: Frame, s: int) -> np.ndarray:
+        """rt_cpu_render_ss: as Context.render_ss, on host threads."""
+        out = np.zeros((ss_rows(frame, s), frame.width // s, 4), np.uint8)
+        _check("rt_cpu_render_ss", lib().rt_cpu_render_ss(self._h, ctypes.byref(frame), s, out.ctypes.data),
+               self._err)
+        return out
+
+    def render_ss_float(self, frame: Frame, s: int) -> np.ndarray:
+        out = np.zeros((ss_rows(frame, s), frame.width // s, 3), np.float32)
+        _check("rt_cpu_render_ss_float",
+               lib().rt_cpu_render_ss_float(self._h, ctypes.byref(frame), s, out.ctypes.data), self._err)
+        return out
+
     def stats(self) -> Stats:
         s = Stats()
         _check("rt_last_stats", lib().rt_last_stats(self._h, ctypes.byref(s)))
@@ -380,6 +435,7 @@ class CScene:
             raise ValueError("backend is 'hip' or 'cpu'")
         self._backend, self._threads = backend, threads
         self._w, self._h = 512, 256          # Var.cpp:4-5
+        self._ss = 1                         # AjusterSurEchantillonnage
         self._max_bounces = 20               # Scene.cpp:68
         self._min_energy = 0.01              # Scene.cpp:69
         self._scene_ior = 1.0                # Scene.cpp:70
@@ -391,6 +447,16 @@ class CScene:
     def AjusterResolution(self, w: int, h: int):
         self._w, self._h = int(w), int(h)
         self._scene = None
+
+    def AjusterSurEchantillonnage(self, s: int):
+        """Supersampling factor (not in the reference): LancerRayons returns
+        the W x H image resolved from s x s samples per pixel — the scene is
+        prepared at s W x s H and rendered by render_ss."""
+        if not 1 <= int(s) <= 8:
+            raise ValueError("the supersampling factor is 1..8")
+        if int(s) != self._ss:
+            self._scene = None
+        self._ss = int(s)
 
     def AjusterNbRebondsMax(self, n: int):
         self._max_bounces = int(n)
@@ -409,7 +475,8 @@ class CScene:
         if self._path is None:
             raise RtError("LancerRayons", -4, "no scene file (TraiterFichierDeScene)")
         if self._scene is None:
-            self._scene = Scene(self._path, self._w, self._h, self._max_bounces, self._min_energy, self._scene_ior)
+            self._scene = Scene(self._path, self._w * self._ss, self._h * self._ss, self._max_bounces,
+                                self._min_energy, self._scene_ior)
             if self._ctx is None:
                 self._ctx = Context(self._device) if self._backend == "hip" else CpuContext(self._threads)
             self._ctx.upload(self._scene)
@@ -423,9 +490,9 @@ class CScene:
     def LancerRayons(self) -> np.ndarray:
         """Render the frame; returns RGBA8 (H, W, 4), row 0 = bottom."""
         f = self._frame()
-        return self._ctx.render(f)
+        return self._ctx.render(f) if self._ss == 1 else self._ctx.render_ss(f, self._ss)
 
     def LancerRayonsFloat(self) -> np.ndarray:
         """m_InfoPixel equivalent: float32 (H, W, 3), unclamped."""
         f = self._frame()
-        return self._ctx.render_float(f)
+        return self._ctx.render_float(f) if self._ss == 1 else self._ctx.render_ss_float(f, self._ss)
