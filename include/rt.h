@@ -347,6 +347,14 @@ enum {
  * float samples stay within 224 MiB each (one chunk up to 3840 x 2160
  * samples and beyond; two at 7680 x 4320).  Never changes an image. */
 #define RT_OPT_SS_CHUNK_ROWS 20
+/* Added within ABI 8 (a macro like the one above).  Launch: the launch-camera
+ * kernels (RT_OPT_LAUNCH_CAMERA) skip a shadow ray's light-buffer cell lookup
+ * where its direction from the light lies outside the cone — found at upload,
+ * carried in the light's record — that contains every cell of that light's
+ * buffer holding an entry: 1 (default) / 0 (every ray looks its cell up).
+ * A skipped lookup would have read an empty list: never changes an image or
+ * a tally. */
+#define RT_OPT_LB_REGION 21
 int rt_set_option(rt_ctx*, int32_t option, double value);
 int rt_get_option(rt_ctx*, int32_t option, double* value);
 /* ABI 4, upload: the far light-buffer ladder of big lists — rising distance

@@ -90,6 +90,27 @@ int rt_debug_selftest(int device, int blocks, unsigned* failures);
 int rt_debug_resolve(rt_ctx*, const float* samples_dev, int width, int s, int rows_out, float* rgb_dev,
                      unsigned* rgba_dev, void* hip_stream);
 
+/* The launch-camera light records' occupied-direction bounds (RT_OPT_LB_REGION;
+ * synchronous): per light j (while 6 j + 5 < n) out[6 j ..] = [a.x, a.y, a.z,
+ * cosB, cells of the light's first buffer that hold an entry, violations].  A
+ * violation is such a cell whose cone (the directions the lookup can map to
+ * it) is not inside the stored float cone [a, cosB] with the test's rounding
+ * allowance, counted by one device thread per cell; cosB = -2: the light
+ * always looks, 2: never.  RT_E_STATE where the uploaded scene has no such
+ * records (not a launch-camera scene). */
+int rt_debug_lb_region(rt_ctx*, double* out, int n);
+
+/* Light `light`'s first light buffer's cell offsets read back (synchronous):
+ * n = 6 R^2 + 1 words (R: rt_debug_lb_info), cell c's entries are
+ * [out[c], out[c + 1]).  RT_E_STATE without a light buffer. */
+int rt_debug_lb_offsets(rt_ctx*, int light, unsigned* out, int n);
+
+/* That bound's host builder alone, no device: off = one buffer's cell offsets
+ * (6 R^2 + 1 rising words; cell c holds an entry when off[c + 1] > off[c];
+ * c = (face R + j) R + i); out5 = [a.x, a.y, a.z, cosB, cells that hold an
+ * entry]. */
+int rt_debug_lb_region_build(const unsigned* off, int R, double* out5);
+
 #ifdef RT_PROF
 /* Only in a library built with -DRT_PROF (tools/prof_sections.py,
  * tools/prof_tiles.py): per-section shader-clock totals and event counts

@@ -866,7 +866,10 @@ struct rt_ctx {
     float4* d_lb_meta = nullptr;
     // the launch-camera kernels' per-light records (rt_shade.h kLightRec) and
     // the host copies they and the launch record are made from
+    // (two sets of n_lights records: with each light's occupied-direction
+    // bound, then with "always look" for RT_OPT_LB_REGION 0)
     float4* d_lrec = nullptr;
+    std::vector<float4> h_lrec;  // the first set (rt_debug_lb_region)
     std::vector<float4> h_lb_meta;
     std::vector<float> h_plane;  // plane[]: [n cst] [file index 0 0 0] per plane
     bool lb_ready = false;
@@ -985,6 +988,7 @@ struct rt_ctx {
     int opt_xcd_deal = 1;       // RT_OPT_XCD_DEAL
     int opt_xcd_stripe = 0;     // RT_OPT_XCD_STRIPE
     bool opt_lb_unroll = true;  // RT_OPT_LB_UNROLL
+    bool opt_lb_region = true;  // RT_OPT_LB_REGION
     float kr_max = 0.0f, kt_max = 0.0f;  // max Kr, max Kt over surfaces
     bool uploaded = false;
     rt_stats last{};
@@ -1175,6 +1179,7 @@ RT_EXPORT int rt_set_option(rt_ctx* c, int32_t opt, double v)
         c->opt_xcd_deal = (int)v;
         return RT_OK;
     case RT_OPT_LB_UNROLL: c->opt_lb_unroll = v != 0; return RT_OK;
+    case RT_OPT_LB_REGION: c->opt_lb_region = v != 0; return RT_OK;
     case RT_OPT_XCD_STRIPE:
         if (v < 0 || v > 4096 || v != std::floor(v)) return RT_E_ARG;
         c->opt_xcd_stripe = (int)v;
@@ -1212,6 +1217,7 @@ RT_EXPORT int rt_get_option(rt_ctx* c, int32_t opt, double* v)
     case RT_OPT_XCD_DEAL: *v = c->opt_xcd_deal; return RT_OK;
     case RT_OPT_XCD_STRIPE: *v = c->opt_xcd_stripe; return RT_OK;
     case RT_OPT_LB_UNROLL: *v = c->opt_lb_unroll ? 1 : 0; return RT_OK;
+    case RT_OPT_LB_REGION: *v = c->opt_lb_region ? 1 : 0; return RT_OK;
     case RT_OPT_SS_CHUNK_ROWS: *v = c->opt_ss_chunk_rows; return RT_OK;
     default: return RT_E_ARG;
     }
@@ -1694,6 +1700,68 @@ done:
     return rc;
 }
 
+// The occupied-direction bound [a.x a.y a.z cosB] of one light buffer
+// (rt_lightbuf.h) from its cell offsets (6 R^2 + 1 words), in double: the
+// axis a is the mean of the centre directions of the cells that hold an
+// entry, rounded to float; B the largest angle(a, w) + W over those cells,
+// grown by 1e-9 (relative and absolute: the check's libm is another one).
+// Only the cells whose centre lies within two cell radii of the farthest
+// centre from a can set B (a cell's W is at most the face-centre cell's),
+// so only their cones are computed: a buffer with thousands of such cells
+// costs a square root per cell, not four atan2.  Returns the number of cells
+// that hold an entry.
+static unsigned lb_region_build(const unsigned* off, int R, float* out4)
+{
+    out4[0] = out4[1] = out4[2] = 0.0f;
+    out4[3] = -2.0f;
+    const int n = 6 * R * R;
+    auto centre = [R](int c, double* w) {
+        lb_face_dir(c / (R * R), (2.0 * (c % R) + 1.0) / R - 1.0, (2.0 * (c / R % R) + 1.0) / R - 1.0, w);
+    };
+    double sum[3] = {0.0, 0.0, 0.0}, w[3];
+    unsigned cnt = 0;
+    for (int c = 0; c < n; ++c) {
+        if (!(off[c + 1] > off[c])) continue;
+        centre(c, w);
+        sum[0] += w[0], sum[1] += w[1], sum[2] += w[2];
+        ++cnt;
+    }
+    if (cnt == 0) {
+        out4[3] = 2.0f;
+        return 0;
+    }
+    const double len = std::sqrt(sum[0] * sum[0] + sum[1] * sum[1] + sum[2] * sum[2]);
+    if (!(len > 0.25 * cnt)) return cnt;  // directions all around the light: no usable axis, always look
+    const float af[3] = {(float)(sum[0] / len), (float)(sum[1] / len), (float)(sum[2] / len)};
+    const double a[3] = {(double)af[0], (double)af[1], (double)af[2]};
+    const double an = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    double dmin = 1.0;  // the farthest centre from a, as a cosine
+    for (int c = 0; c < n; ++c) {
+        if (!(off[c + 1] > off[c])) continue;
+        centre(c, w);
+        dmin = std::min(dmin, (a[0] * w[0] + a[1] * w[1] + a[2] * w[2]) / an);
+    }
+    const double far = std::acos(std::max(-1.0, dmin));
+    if (!(far < 1.0)) return cnt;
+    const double wmax = lb_cone_d(0, R / 2, R / 2 + 1, R / 2, R / 2 + 1, R, 0.0, w);
+    const double dscreen = std::cos(std::max(0.0, far - 2.0 * wmax)) + 1e-12;
+    double B = 0.0;
+    for (int c = 0; c < n; ++c) {
+        if (!(off[c + 1] > off[c])) continue;
+        centre(c, w);
+        if ((a[0] * w[0] + a[1] * w[1] + a[2] * w[2]) / an > dscreen) continue;
+        const double W = lb_cone_d(c / (R * R), c % R, c % R + 1, c / R % R, c / R % R + 1, R, 0.0, w);
+        B = std::max(B, lb_region_need(a, w, W));
+    }
+    B = B * (1.0 + 1e-9) + 1e-9;
+    if (!(B < 1.0)) return cnt;
+    const double cw = lb_region_cos(B);
+    float cf = (float)cw;
+    if ((double)cf > cw) cf = std::nextafterf(cf, -INFINITY);
+    out4[0] = af[0], out4[1] = af[1], out4[2] = af[2], out4[3] = cf;
+    return cnt;
+}
+
 RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
 {
     if (!c || !s || s->n_surfaces < 0 || s->n_lights < 0) return RT_E_ARG;
@@ -1836,6 +1904,7 @@ RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
     c->d_lb_off = nullptr;
     c->d_lb_ent = c->d_lb_dcap = c->d_lb_meta = c->d_lrec = nullptr;
     c->h_lb_meta.clear();
+    c->h_lrec.clear();
     c->lb_ready = false;
     c->lb_levels = 0;
     c->lb_r0 = 0;
@@ -2091,18 +2160,46 @@ RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
     HIP_TRY(c, hipMemcpy(c->d_mat, mat.data(), mat.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_lights, lig.data(), lig.size() * sizeof(float), hipMemcpyHostToDevice));
     // The launch-camera kernels' light records (rt_shade.h): per light its
-    // lights[] pair and its first buffer's lb_meta pair in 64 bytes,
-    // [x y z I] [r g b dcov] [off base, dcap base, n dcap, R] [0 0 0 0].
+    // lights[] pair, its first buffer's lb_meta pair and that buffer's
+    // occupied-direction bound (lb_region_build, from the buffers' cell
+    // offsets read back once) in 64 bytes,
+    // [x y z I] [r g b dcov] [off base, dcap base, n dcap, R] [a.x a.y a.z cosB];
+    // then the same records with [0 0 0 -2] ("always look", RT_OPT_LB_REGION 0).
     c->h_plane = pla;
     if (c->lb_ready && ntr <= (size_t)kTinyMax && c->h_lb_meta.size() >= 2 * (size_t)nl) {
-        std::vector<float4> lr((size_t)kLightRec * nl);
+        std::vector<float4> lr((size_t)kLightRec * nl * 2);
+        // the lights' first buffers' offsets (consecutive slices of lb_off): one copy
+        std::vector<unsigned> off;
+        size_t lo = SIZE_MAX, hi = 0;
+        for (int j = 0; j < nl; ++j) {
+            unsigned obase;
+            int R;
+            std::memcpy(&obase, &c->h_lb_meta[2 * j].x, 4);
+            std::memcpy(&R, &c->h_lb_meta[2 * j].w, 4);
+            if (R <= 0) continue;
+            lo = std::min(lo, (size_t)obase);
+            hi = std::max(hi, (size_t)obase + 6 * (size_t)R * R + 1);
+        }
+        if (hi > lo) {
+            off.resize(hi - lo);
+            HIP_TRY(c, hipMemcpy(off.data(), c->d_lb_off + lo, off.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+        }
         for (int j = 0; j < nl; ++j) {
             const float* l = &lig[8 * (size_t)j];
             lr[kLightRec * j] = make_float4(l[0], l[1], l[2], l[3]);
             lr[kLightRec * j + 1] = make_float4(l[4], l[5], l[6], c->h_lb_meta[2 * j + 1].x);
             lr[kLightRec * j + 2] = c->h_lb_meta[2 * j];
-            lr[kLightRec * j + 3] = make_float4(0.f, 0.f, 0.f, 0.f);
+            unsigned obase;
+            int R;
+            std::memcpy(&obase, &c->h_lb_meta[2 * j].x, 4);
+            std::memcpy(&R, &c->h_lb_meta[2 * j].w, 4);
+            float rg[4] = {0.f, 0.f, 0.f, -2.0f};
+            if (R > 0) lb_region_build(off.data() + (obase - lo), R, rg);
+            lr[kLightRec * j + 3] = make_float4(rg[0], rg[1], rg[2], rg[3]);
+            for (int q = 0; q < 3; ++q) lr[kLightRec * (nl + j) + q] = lr[kLightRec * j + q];
+            lr[kLightRec * (nl + j) + 3] = make_float4(0.f, 0.f, 0.f, -2.0f);
         }
+        c->h_lrec.assign(lr.begin(), lr.begin() + (size_t)kLightRec * nl);
         HIP_TRY(c, hipMalloc(&c->d_lrec, lr.size() * sizeof(float4)));
         HIP_TRY(c, hipMemcpy(c->d_lrec, lr.data(), lr.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
@@ -2301,7 +2398,7 @@ static int launch_trace(rt_ctx* c, const KernelPick& kp, const TinyCam* T, bool 
             std::memcpy(&H.pidx[k], &p[4], sizeof(int));
         }
         H.rgba = oa, H.rgbf = ob, H.stats = stats;
-        H.geom = S.geom, H.mat = S.mat, H.lrec = c->d_lrec, H.planes = S.plane, H.quad = S.quad;
+        H.geom = S.geom, H.mat = S.mat, H.lrec = c->d_lrec + (c->opt_lb_region ? 0 : kLightRec * S.n_lights), H.planes = S.plane, H.quad = S.quad;
         H.translucent = S.translucent;
         H.lb_off = S.lb_off, H.lb_ent = S.lb_ent, H.lb_dcap = S.lb_dcap, H.cone_light = S.cone_light, H.tri = S.tri;
         H.n_lights = S.n_lights, H.n_tri = S.n_tri, H.n_tri_opaque = S.n_tri_opaque;
@@ -3564,6 +3661,77 @@ RT_EXPORT int rt_debug_lb_info(rt_ctx* c, double* out, int n)
         out[4 + 3 * j] = nd;
         out[5 + 3 * j] = meta[2 * j + 1].x;
     }
+    return RT_OK;
+}
+
+// Diagnostic (include/rt_debug.h): the launch-camera light records'
+// occupied-direction bounds, per light [a.x a.y a.z cosB, cells that hold an
+// entry, cells whose cone is outside the stored bound] (rt_lb_region_check).
+RT_EXPORT int rt_debug_lb_region(rt_ctx* c, double* out, int n)
+{
+    if (!c || !out || n < 6) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    const int nl = c->n_lights;
+    if (!c->uploaded || !c->lb_ready || !c->d_lrec || c->h_lrec.size() != (size_t)kLightRec * nl) {
+        c->err = "no launch-camera light records";
+        return RT_E_STATE;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    unsigned* d_cnt = nullptr;
+    HIP_TRY(c, hipMalloc(&d_cnt, 2 * sizeof(unsigned) * (size_t)nl));
+    hipError_t e = hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned) * (size_t)nl, c->stream);
+    for (int j = 0; j < nl && e == hipSuccess; ++j) {
+        unsigned obase;
+        int R;
+        std::memcpy(&obase, &c->h_lrec[kLightRec * j + 2].x, 4);
+        std::memcpy(&R, &c->h_lrec[kLightRec * j + 2].w, 4);
+        if (R <= 0) continue;
+        hipLaunchKernelGGL(rt_lb_region_check, dim3((unsigned)((6 * R * R + 255) / 256)), dim3(256), 0, c->stream,
+                           c->d_lb_off + obase, R, c->h_lrec[kLightRec * j + 3], d_cnt + 2 * j);
+        e = hipGetLastError();
+    }
+    std::vector<unsigned> cnt(2 * (size_t)nl);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipFree(d_cnt);
+    HIP_TRY(c, e);
+    for (int j = 0; j < nl && 6 * j + 5 < n; ++j) {
+        const float4 rg = c->h_lrec[kLightRec * j + 3];
+        out[6 * j] = rg.x, out[6 * j + 1] = rg.y, out[6 * j + 2] = rg.z, out[6 * j + 3] = rg.w;
+        out[6 * j + 4] = cnt[2 * j], out[6 * j + 5] = cnt[2 * j + 1];
+    }
+    return RT_OK;
+}
+
+// Diagnostic (include/rt_debug.h): light `light`'s first buffer's cell
+// offsets (6 R^2 + 1 words, R from rt_debug_lb_info) read back into out.
+RT_EXPORT int rt_debug_lb_offsets(rt_ctx* c, int light, unsigned* out, int n)
+{
+    if (!c || !out || light < 0) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    if (!c->uploaded || !c->lb_ready || light >= c->n_lights || c->h_lb_meta.size() < 2 * (size_t)c->n_lights) {
+        c->err = "no light buffer";
+        return RT_E_STATE;
+    }
+    unsigned obase;
+    int R;
+    std::memcpy(&obase, &c->h_lb_meta[2 * (size_t)light].x, 4);
+    std::memcpy(&R, &c->h_lb_meta[2 * (size_t)light].w, 4);
+    if (R <= 0 || n != 6 * R * R + 1) return RT_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpy(out, c->d_lb_off + obase, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// The bound's host builder alone, no device (rt_debug.h): off = the cell
+// offsets of one buffer (6 R^2 + 1 rising words); out5 = [a.x a.y a.z cosB,
+// cells that hold an entry].
+RT_EXPORT int rt_debug_lb_region_build(const unsigned* off, int R, double* out5)
+{
+    if (!off || !out5 || R <= 0 || R > 1024) return RT_E_ARG;
+    float rg[4];
+    out5[4] = lb_region_build(off, R, rg);
+    for (int q = 0; q < 4; ++q) out5[q] = rg[q];
     return RT_OK;
 }
 

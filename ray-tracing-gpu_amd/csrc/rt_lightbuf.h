@@ -58,7 +58,7 @@ __device__ __forceinline__ int lb_cell(const Vec3 d, int R)
     return (face * R + j) * R + i;
 }
 
-__device__ __forceinline__ void lb_face_dir(int face, double u, double v, double* o)
+__host__ __device__ __forceinline__ void lb_face_dir(int face, double u, double v, double* o)
 {
     switch (face) {
     case 0: o[0] = 1.0; o[1] = u; o[2] = v; break;
@@ -77,13 +77,14 @@ __device__ __forceinline__ void lb_face_dir(int face, double u, double v, double
 // The farthest point of a small geodesically convex cell from its centre
 // direction is a corner.  Float |d| = 1 within 1e-6 (sqrt_w/recip_w), float
 // w within 1.2e-7 of the unit centre: cosW = cos(W)(1 - 2e-6) - 4e-6 keeps
-// exact w.d >= cosW + 2e-6 for every direction of the cells.
-__device__ WaveCone lb_cone(int face, int i0, int i1, int j0, int j1, int R, double widen)
+// exact w.d >= cosW + 2e-6 for every direction of the cells.  lb_cone_d: the
+// unit centre w and the half-angle W in double (host too: lb_region_build).
+__host__ __device__ __forceinline__ double lb_cone_d(int face, int i0, int i1, int j0, int j1, int R, double widen,
+                                                     double* w)
 {
     const double du = 1e-5;
     const double u0 = 2.0 * i0 / R - 1.0 - du, u1 = 2.0 * i1 / R - 1.0 + du;
     const double v0 = 2.0 * j0 / R - 1.0 - du, v1 = 2.0 * j1 / R - 1.0 + du;
-    double w[3];
     lb_face_dir(face, 0.5 * (u0 + u1), 0.5 * (v0 + v1), w);
     double W = 0.0;
     for (int q = 0; q < 4; ++q) {
@@ -92,7 +93,13 @@ __device__ WaveCone lb_cone(int face, int i0, int i1, int j0, int j1, int R, dou
         const double x = w[1] * c[2] - w[2] * c[1], y = w[2] * c[0] - w[0] * c[2], z = w[0] * c[1] - w[1] * c[0];
         W = fmax(W, atan2(sqrt(x * x + y * y + z * z), w[0] * c[0] + w[1] * c[1] + w[2] * c[2]));
     }
-    W = W * (1.0 + 1e-9) + 1e-6 + widen;
+    return W * (1.0 + 1e-9) + 1e-6 + widen;
+}
+
+__device__ WaveCone lb_cone(int face, int i0, int i1, int j0, int j1, int R, double widen)
+{
+    double w[3];
+    const double W = lb_cone_d(face, i0, i1, j0, j1, R, widen, w);
     WaveCone k;
     k.w = make3((float)w[0], (float)w[1], (float)w[2]);
     const double cw = cos(W) * (1.0 - 2e-6) - 4e-6;
@@ -273,6 +280,47 @@ __global__ void rt_lb_dcap(const float4* __restrict__ cone, const float4* __rest
     const int k = perm[q];
     const float4 c1 = cone[2 * k + 1];
     lb_write(out + kLbEntF * (size_t)q, tri, k, c1.z == c1.z ? c1.z : -INFINITY);
+}
+
+// ---- occupied-direction bound of a light's first buffer (rt_shade.h kLightRec)
+// The launch-camera kernels skip the cell lookup of a lane whose direction
+// from the light d = -L fails fl(d . a) >= cosB, where the cone [a, B]
+// contains the cone [w, W] (lb_cone_d) of every cell that holds an entry:
+// angle(a, w) + W <= B.  A float direction the lookup can map to such a cell
+// lies within W of w, hence within B of a; |d| = 1 within 1e-6, float a
+// within 1.2e-7 of its double, the float dot within 4e-7: cosB = cos(B)
+// (1 - 2e-6) - 4e-6, rounded down (lb_cone's recipe), is below fl(d . a).  So
+// a lane that skips would have read an empty list.  cosB = 2: no cell holds
+// an entry (never looks); cosB = -2: B >= 1 rad or no usable axis (always
+// looks).
+// The half-angle about the axis a that the cell cone (w, W) needs.
+__host__ __device__ __forceinline__ double lb_region_need(const double* a, const double* w, double W)
+{
+    const double x = a[1] * w[2] - a[2] * w[1], y = a[2] * w[0] - a[0] * w[2], z = a[0] * w[1] - a[1] * w[0];
+    return atan2(sqrt(x * x + y * y + z * z), a[0] * w[0] + a[1] * w[1] + a[2] * w[2]) + W;
+}
+// The stored cosine of the half-angle B (< 1 rad), before its rounding down to float.
+__host__ __device__ __forceinline__ double lb_region_cos(double B) { return cos(B) * (1.0 - 2e-6) - 4e-6; }
+
+// rt_debug_lb_region's check, one thread per cell of the buffer at off (6 R^2
+// + 1 words): out[0] += cells that hold an entry, out[1] += those whose cone
+// is not inside the stored float bound rg = [a, cosB].
+__global__ void rt_lb_region_check(const unsigned* __restrict__ off, int R, float4 rg, unsigned* __restrict__ out)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= 6 * R * R) return;
+    if (!(off[c + 1] > off[c])) return;
+    atomicAdd(&out[0], 1u);
+    const int face = c / (R * R), j = c / R % R, i = c % R;
+    double w[3];
+    const double W = lb_cone_d(face, i, i + 1, j, j + 1, R, 0.0, w);
+    const double a[3] = {(double)rg.x, (double)rg.y, (double)rg.z};
+    bool inside = rg.w == -2.0f;
+    if (!inside && rg.w <= 1.0f) {
+        const double B = lb_region_need(a, w, W);
+        inside = B < 1.0 && lb_region_cos(B) >= (double)rg.w;
+    }
+    if (!inside) atomicAdd(&out[1], 1u);
 }
 
 }  // namespace rt

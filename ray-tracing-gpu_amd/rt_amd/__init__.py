@@ -24,7 +24,7 @@ import numpy as np
 
 __all__ = [
     "RtError", "SceneFlat", "Frame", "Stats", "Scene", "Context", "CpuContext", "CScene", "lib", "band_rows",
-    "frame_rows", "ss_rows", "SS_OPTIONS",
+    "frame_rows", "ss_rows", "SS_OPTIONS", "LB_OPTIONS",
     "LIB_PATH", "TRIANGLE", "PLANE", "QUADRIC", "FLAG_STATS", "OPTIONS", "camera_path",
 ]
 
@@ -39,6 +39,8 @@ OPTIONS = {"light_buffer": 1, "camera_buffer": 2, "union_pretest": 3, "lb_scale"
            "wf_sort": 15, "xcd_deal": 16, "xcd_stripe": 17, "lb_unroll": 18, "wf_overlap": 19}
 # rt.h's additions within ABI 8 (macros beside the RT_OPT_* enum): set_option / get_option take these names too
 SS_OPTIONS = {"ss_chunk_rows": 20}
+# (RT_OPT_LB_REGION: the launch-camera kernels' occupied-direction test, 1 / 0)
+LB_OPTIONS = {"lb_region": 21}
 _ERRORS = {-1: "RT_E_ARG", -2: "RT_E_IO", -3: "RT_E_PARSE", -4: "RT_E_STATE", -5: "RT_E_HIP",
            -6: "RT_E_UNSUPPORTED"}
 
@@ -159,7 +161,10 @@ def ss_rows(frame: "Frame", s: int) -> int:
 
 def _option(name) -> int:
     if isinstance(name, str):
-        return OPTIONS[name] if name in OPTIONS else SS_OPTIONS[name]
+        for table in (OPTIONS, SS_OPTIONS, LB_OPTIONS):
+            if name in table:
+                return table[name]
+        raise KeyError(name)
     return int(name)
 
 
@@ -256,7 +261,7 @@ class Context:
                 self.set_option(k, v)
 
     def set_option(self, name, value: float):
-        """rt_set_option: `name` is a key of OPTIONS or SS_OPTIONS (or the RT_OPT_* number)."""
+        """rt_set_option: `name` is a key of OPTIONS, SS_OPTIONS or LB_OPTIONS (or the RT_OPT_* number)."""
         opt = _option(name)
         _check("rt_set_option", lib().rt_set_option(self._h, opt, float(value)), self._err)
 
