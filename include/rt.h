@@ -259,6 +259,55 @@ int rt_cpu_render_ss_float(rt_ctx*, const rt_frame* samples, int32_t s, float* r
 /* Output rows of a supersampled render; -1 if the (frame, s) pair is invalid. */
 int32_t rt_ss_rows(const rt_frame* samples, int32_t s);
 
+/* Primary-hit AOV renders (arbitrary output variables) — an addition within
+ * ABI 8 (rt_abi_version() stays 8; test for RT_HAS_AOV).  One pass of primary
+ * rays only, no shading: per pixel what CScene::ObtenirCouleur's search
+ * (Scene.cpp:1705-1715) holds in `Result` when it leaves its loop.
+ * Definition.  For pixel (px, py) of the frame the ray is the plain render's
+ * (Scene.cpp:1543-1552).  Over the surfaces in file order, surface i with
+ * distance t_i replaces the current winner when
+ *   t_i > EPSILON && (t_i < t_best || t_best < 0)
+ * (a tie keeps the earlier surface).  The planes, each (rows x width), planar:
+ *   t   float32      the winner's ObtenirDistance()
+ *   id  int32        the winner's file index (rt_scene_flat order)
+ *   n   3 x float32  the winner's ObtenirNormale(): triangles and planes the
+ *                    stored post-Pretraitement normal, NOT flipped towards
+ *                    the ray; quadrics the normalised gradient at the hit
+ *   miss: id = -1, t = -1.0f, n = (0, 0, 0) — the reference's empty
+ *   CIntersection (Intersection.cpp:17-18).
+ * max_bounces, min_energy, scene_ior, the background and the lights play no
+ * part.  Rows, slabs and bands are packed exactly as by rt_render_float: row
+ * 0 is the bottom row, and a band row past the frame stays unwritten.
+ * Each plane pointer may be NULL (not all three).  rt_render_aov is
+ * synchronous and takes a host or a device pointer per plane;
+ * rt_render_aov_async takes device pointers and follows rt_render_async's
+ * ordering and capture rules (ABI 4 / 5): per-camera state is made current
+ * on `hip_stream`; inside a hipGraph capture only the AOV kernel is recorded,
+ * RT_E_STATE if it needs camera state that is not current.  Scenes whose
+ * colour frames take their camera records with the launch
+ * (RT_OPT_LAUNCH_CAMERA) and scenes without triangles need no camera state:
+ * their AOV pass never builds or invalidates any.  The other scenes run the
+ * culling of their depth-0 colour frame (RT_OPT_CAMERA_BUFFER,
+ * RT_OPT_CB_CAPACITY and RT_OPT_XCD_DEAL apply), so the AOV hit is the colour
+ * image's primary hit by construction (rt_aov_kernel, csrc/rt_aov.h).
+ * RT_E_ARG: all three planes NULL, RT_FLAG_STATS set, a bad slab / band.
+ * RT_E_STATE: before rt_upload_scene, or on the other backend's context
+ * (rt_cpu_render_aov is the CPU backend's: the same bits).
+ * rt_last_stats after the synchronous call: kernel_ms the AOV kernel's time,
+ * kernel its name and variant (e.g. "rt_aov_kernel<10>"), primary_rays the
+ * pixels written, everything else 0.
+ * Supersampling: an AOV render of the sample frame is the AOVs of the sample
+ * grid; there is no resolve of AOVs. */
+#define RT_HAS_AOV 1
+typedef struct rt_aov {
+    float* t;
+    int32_t* id;
+    float* n;
+} rt_aov; /* each may be NULL, not all */
+int rt_render_aov(rt_ctx*, const rt_frame*, const rt_aov* out);  /* sync; host or device ptr per plane */
+int rt_render_aov_async(rt_ctx*, const rt_frame*, const rt_aov* dev, void* hip_stream); /* device ptrs */
+int rt_cpu_render_aov(rt_ctx*, const rt_frame*, const rt_aov* out);                     /* CPU backend */
+
 /* ABI 4: context options.  A/B and test switches and tuning knobs; no option
  * changes a single bit of any image.  Upload options take effect at the next
  * rt_upload_scene, launch options at the next render.                      */

@@ -388,6 +388,52 @@ int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uin
     return RT_OK;
 }
 
+// The AOV pass (rt.h rt_render_aov): the primary hit of every pixel, the
+// kernel's values bit for bit (the same closest / normal_of the colour path
+// uses).  A miss is the reference's empty CIntersection.
+int cpu_render_aov(const void* handle, int threads, const rt_frame* f, int rows, float* out_t, int32_t* out_id,
+                   float* out_n, double* ms)
+{
+    using namespace cpu;
+    const Scene& S = *static_cast<const Scene*>(handle);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int W = f->width;
+    const Vec3 O = make3(f->cam_pos[0], f->cam_pos[1], f->cam_pos[2]);
+    std::atomic<int> next{0};
+    constexpr int kBand = 8;
+    auto work = [&]() {
+        for (;;) {
+            const int q0 = next.fetch_add(kBand);
+            if (q0 >= rows) return;
+            for (int q = q0; q < std::min(rows, q0 + kBand); ++q) {
+                const int y = out_row(*f, q);
+                if (y >= f->height) continue;  // a band row past the frame: left unwritten, like the kernel
+                for (int x = 0; x < W; ++x) {
+                    const size_t o = (size_t)q * W + x;
+                    const Vec3 D = camera_dir(*f, x, y);
+                    const Hit h = closest(S, O, D);
+                    if (out_t) out_t[o] = h.file < 0 ? -1.0f : h.t;
+                    if (out_id) out_id[o] = h.file;
+                    if (out_n) {
+                        const Vec3 N = h.file < 0 ? make3(0.0f, 0.0f, 0.0f) : normal_of(S, h.file, O, D, h.t);
+                        out_n[3 * o] = N.x;
+                        out_n[3 * o + 1] = N.y;
+                        out_n[3 * o + 2] = N.z;
+                    }
+                }
+            }
+        }
+    };
+    int n = threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency());
+    n = std::max(1, std::min(n, (rows + kBand - 1) / kBand));
+    std::vector<std::thread> pool;
+    for (int i = 1; i < n; ++i) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
 void cpu_resolve(const float* samples, int width, int s, int rows_out, uint8_t* rgba, float* rgb, double* ms)
 {
     const auto t0 = std::chrono::steady_clock::now();

@@ -12,6 +12,10 @@ void cpu_free(void* handle);
 // Render `rows` output rows of frame f (slab or band set) on `threads` host
 // threads (<= 0: all); either output may be null.  *ms = wall time.
 int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uint8_t* rgba8, float* rgb, double* ms);
+// The primary-hit AOV planes of the same rows (rt.h rt_render_aov: t, file
+// index, normal; a miss is -1, -1, 0); each output may be null.
+int cpu_render_aov(const void* handle, int threads, const rt_frame* f, int rows, float* t, int32_t* id, float* n,
+                   double* ms);
 // The supersampling resolve (rt_resolve.h resolve_px, the HIP kernel's own
 // arithmetic): rows_out rows of width / s pixels from their packed sample
 // rows; either output may be null.  *ms = wall time.

@@ -759,6 +759,8 @@ __global__ __launch_bounds__(64) void rt_bvh_wave_kernel(const SceneDev S, const
 
 }  // namespace rt
 
+#include "rt_aov.h"  // rt_aov_kernel (needs tile_of_block above)
+
 // ===================================================================== host
 using namespace rt;
 
@@ -2343,19 +2345,18 @@ static const void* tiny_kernel(int mode)
                        : (const void*)&rt_trace_tiny<0, 1, 37, COUNT>;
 }
 
-// One trace launch over `rows` output rows (T: the launch-camera kernel with
-// its records, else kernel k).
-static int launch_trace(rt_ctx* c, const KernelPick& kp, const TinyCam* T, bool count, SceneDev& S, FrameDev& F,
-                        int width, int rows, unsigned* oa, float* ob, StatsDev* stats, hipStream_t st, int mode = 0)
+// The launch grid over `rows` output rows and the frame's tile-dealing fields
+// (tile_of_block); big: a big-list kernel (WAVE bit 2), whose RT_OPT_XCD_DEAL
+// modes other than 1 launch padded grids.
+static void trace_grid(const rt_ctx* c, bool big, FrameDev& F, int width, int rows, dim3& grid, dim3& block)
 {
-    dim3 grid, block;
     trace_dims(width, rows, grid, block);
     F.tiles_x = (int)grid.x;
     F.tiles_y = (int)grid.y;
     F.xcd_mode = 1;
     F.xcd_w = 0;
     F.xcd_m = 0;
-    if (!T && (kp.wave & 2) && c->opt_xcd_deal != 1) {
+    if (big && c->opt_xcd_deal != 1) {
         // the big-list kernels' padded grids (tile_of_block)
         F.xcd_mode = c->opt_xcd_deal;
         if (c->opt_xcd_deal == 2) {
@@ -2370,6 +2371,15 @@ static int launch_trace(rt_ctx* c, const KernelPick& kp, const TinyCam* T, bool 
             grid = dim3(8, nst);
         }
     }
+}
+
+// One trace launch over `rows` output rows (T: the launch-camera kernel with
+// its records, else kernel k).
+static int launch_trace(rt_ctx* c, const KernelPick& kp, const TinyCam* T, bool count, SceneDev& S, FrameDev& F,
+                        int width, int rows, unsigned* oa, float* ob, StatsDev* stats, hipStream_t st, int mode = 0)
+{
+    dim3 grid, block;
+    trace_grid(c, !T && (kp.wave & 2), F, width, rows, grid, block);
     if (T) {
         // the launch record (rt_cull.h TinyLaunch): the frame's, the scene's
         // and the camera records' wave-uniform values, one argument
@@ -3590,6 +3600,155 @@ RT_EXPORT int rt_cpu_render_ss(rt_ctx* c, const rt_frame* f, int32_t s, uint8_t*
 RT_EXPORT int rt_cpu_render_ss_float(rt_ctx* c, const rt_frame* f, int32_t s, float* rgb_out)
 {
     return cpu_render_ss_sync(c, f, s, nullptr, rgb_out);
+}
+
+// ---- primary-hit AOV renders (rt.h, rt_aov.h)
+typedef void (*aov_fn)(const SceneDev, const FrameDev, float*, int*, float*);
+static aov_fn aov_kernel(int wave)
+{
+    switch (wave) {
+    case 1: return &rt_aov_kernel<1>;
+    case 9: return &rt_aov_kernel<9>;
+    case 2: return &rt_aov_kernel<2>;
+    case 10: return &rt_aov_kernel<10>;
+    default: return &rt_aov_kernel<0>;
+    }
+}
+
+// The checks every AOV entry point shares (after the backend's own).
+static int aov_check(rt_ctx* c, const rt_frame* f, const rt_aov* o)
+{
+    if (!c->uploaded) {
+        c->err = "render before rt_upload_scene";
+        return RT_E_STATE;
+    }
+    if (!o->t && !o->id && !o->n) {
+        c->err = "rt_render_aov: no output plane requested";
+        return RT_E_ARG;
+    }
+    if (f->flags & RT_FLAG_STATS) {
+        c->err = "rt_render_aov: RT_FLAG_STATS is not accepted";
+        return RT_E_ARG;
+    }
+    if (!frame_ok(f)) {
+        c->err = "bad rt_frame geometry";
+        return RT_E_ARG;
+    }
+    return RT_OK;
+}
+
+// One AOV frame into device planes on st.  The variant: WAVE 0 (no camera
+// state) for the scenes whose colour frames take their camera records with
+// the launch — no camera state is built or invalidated behind that kernel —
+// and for scenes without triangles; else the depth-0 colour frame's culling
+// (wave, or clustered above kClusterMinTriangles) with the camera state made
+// current exactly as rt_render / rt_render_async do (prepare_state), the
+// camera buffer where it is current (a tile whose list did not fit: the
+// per-wave path).  sync_path: rt_render_aov on c->stream, timed.
+static int launch_aov(rt_ctx* c, const rt_frame* f, const rt_aov& dev, hipStream_t st, bool sync_path)
+{
+    bool capturing = false;
+    if (!sync_path) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIP_TRY(c, hipStreamIsCapturing(st, &cs));
+        capturing = cs != hipStreamCaptureStatusNone;
+    }
+    const bool wave0 = c->n_tri == 0 || tiny_ok(c, 0, lbuf_on(c));
+    const bool cb_want = !wave0 && c->opt_camera_buffer && cb_frame_ok(f);
+    const int rows = frame_rows(f);
+    if (rows > 0 && !wave0) {
+        if (int rc = prepare_state(c, f, st, sync_path, capturing, cb_want)) return rc;
+    }
+    const bool cbuf = cb_want && cb_matches(c->cb, f);
+    const int wave = wave0 ? 0 : ((c->n_tri > kClusterMinTriangles ? 2 : 1) | (cbuf ? 8 : 0));
+    SceneDev S = scene_dev(c, false, cbuf);
+    FrameDev F;
+    frame_dev(f, F);
+    c->last = rt_stats{};
+    std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_aov_kernel<%d>", wave);
+    c->last.primary_rays = (uint64_t)f->width * (uint64_t)ss_valid_rows(f, rows);
+    if (rows == 0) return RT_OK;
+    dim3 grid, block;
+    trace_grid(c, (wave & 2) != 0, F, f->width, rows, grid, block);
+    float* ot = dev.t;
+    int* oi = dev.id;
+    float* on = dev.n;
+    void* args[] = {&S, &F, &ot, &oi, &on};
+    if (sync_path) HIP_TRY(c, hipEventRecord(c->ev0, st));
+    HIP_TRY(c, hipLaunchKernel((const void*)aov_kernel(wave), grid, block, args,
+                               (wave & 2) ? (unsigned)kLdsWaveBytes : 0u, st));
+    if (sync_path) HIP_TRY(c, hipEventRecord(c->ev1, st));
+    if (capturing) {
+        c->captured = true;
+        if (cbuf) c->cb.pinned = true;
+    } else if (!sync_path) {
+        note_async(c, st);
+    }
+    return RT_OK;
+}
+
+RT_EXPORT int rt_render_aov(rt_ctx* c, const rt_frame* f, const rt_aov* out)
+{
+    if (!c || !f || !out) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    if (int rc = aov_check(c, f, out)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = fence_async(c, c->stream)) return rc;
+    if (int rc = wait_state(c, c->stream)) return rc;
+    // per plane: a device pointer is written in place, a host pointer through
+    // the context's scratch (one 256-byte aligned part per host plane)
+    const int rows = std::max(0, frame_rows(f));
+    const size_t px = (size_t)f->width * (size_t)rows;
+    void* const user[3] = {out->t, out->id, out->n};
+    const size_t bytes[3] = {px * 4, px * 4, px * 12};
+    bool host[3] = {false, false, false};
+    size_t off[3] = {0, 0, 0}, need = 0;
+    for (int i = 0; i < 3; ++i) {
+        host[i] = user[i] && !is_device_ptr(user[i]);
+        if (host[i]) {
+            off[i] = need;
+            need += (bytes[i] + 255) / 256 * 256;
+        }
+    }
+    if (need)
+        if (int rc = ensure_scratch(c, need)) return rc;
+    void* target[3];
+    for (int i = 0; i < 3; ++i) target[i] = host[i] ? (void*)((char*)c->d_scratch + off[i]) : user[i];
+    const rt_aov dev{(float*)target[0], (int32_t*)target[1], (float*)target[2]};
+    if (int rc = launch_aov(c, f, dev, c->stream, true)) return rc;
+    // (a band set's rows past the frame are not written: they are not copied either)
+    const size_t wrote = (size_t)f->width * (size_t)ss_valid_rows(f, rows);
+    for (int i = 0; i < 3; ++i)
+        if (host[i] && wrote)
+            HIP_TRY(c, hipMemcpyAsync(user[i], target[i], wrote * (i == 2 ? 12 : 4), hipMemcpyDeviceToHost, c->stream));
+    return finish_sync(c, f, c->stream, rows > 0);
+}
+
+RT_EXPORT int rt_render_aov_async(rt_ctx* c, const rt_frame* f, const rt_aov* dev, void* stream)
+{
+    if (!c || !f || !dev) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    if (int rc = aov_check(c, f, dev)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return launch_aov(c, f, *dev, (hipStream_t)stream, false);
+}
+
+RT_EXPORT int rt_cpu_render_aov(rt_ctx* c, const rt_frame* f, const rt_aov* out)
+{
+    if (!c || !f || !out) return RT_E_ARG;
+    if (!c->cpu) {
+        c->err = "rt_cpu_render_aov needs a CPU context (rt_create_cpu)";
+        return RT_E_STATE;
+    }
+    if (int rc = aov_check(c, f, out)) return rc;
+    c->last = rt_stats{};
+    const int rows = frame_rows(f);
+    double ms = 0.0;
+    const int rc = cpu_render_aov(c->cpu_scene, c->cpu_threads, f, rows, out->t, out->id, out->n, &ms);
+    c->last.kernel_ms = (float)ms;
+    c->last.primary_rays = (uint64_t)f->width * (uint64_t)ss_valid_rows(f, rows);
+    std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_render_aov");
+    return rc;
 }
 
 // Diagnostic (include/rt_debug.h): the resolve kernel alone.

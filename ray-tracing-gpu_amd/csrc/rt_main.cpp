@@ -3,7 +3,7 @@
 //   rt_render <scene.dat> [-x W] [-y H] [-d depth] [-o out.ppm] [-g gpus]
 //             [--device first] [--bands] [-n frames] [-s]
 //             [--gather rccl|host] [--backend hip|cpu] [--threads N]
-//             [--ssaa N]
+//             [--ssaa N] [--aov PREFIX]
 //
 // Kept from Main.cpp:51-199: argv[1] is the scene file, -x / -y set the
 // resolution (default 512x256, Var.cpp:4-5), the same [ETAT]/[ERREUR] log
@@ -34,6 +34,11 @@
 // the same image, the GPU never touched.  --ssaa N (1..8) writes the W x H
 // image resolved from N x N samples per pixel (rt_render_ss / rt_cpu_render_ss:
 // the scene is prepared at N W x N H), on either backend, one GPU.
+// --aov PREFIX also writes the frame's primary-hit buffers (rt_render_aov /
+// rt_cpu_render_aov) as PREFIX_t.npy (float32, H x W), PREFIX_id.npy (int32,
+// H x W) and PREFIX_n.npy (float32, H x W x 3): NumPy format 1.0,
+// little-endian, row 0 = the bottom scanline like the library (with --ssaa:
+// of the N W x N H sample grid); on either backend, one GPU.
 #include <hip/hip_runtime_api.h>
 
 #include <dlfcn.h>
@@ -67,6 +72,52 @@ static int write_ppm(const char* path, int W, int H, const std::vector<uint8_t>&
         for (int x = 0; x < W; ++x) std::fwrite(&img[((size_t)y * W + x) * 4], 1, 3, f);
     std::fclose(f);
     std::printf("[ETAT]: Image ecrite dans %s\n", path);
+    return 0;
+}
+
+// One array as a NumPy format 1.0 file: magic, version, the header's length
+// (little-endian u16) and the header dict padded with spaces to a multiple of
+// 64 bytes, newline last; then the C-order data as they lie in memory.
+static int write_npy(const std::string& path, const char* descr, int rows, int width, int comps, const void* data,
+                     size_t bytes)
+{
+    char shape[64];
+    if (comps > 1)
+        std::snprintf(shape, sizeof shape, "(%d, %d, %d)", rows, width, comps);
+    else
+        std::snprintf(shape, sizeof shape, "(%d, %d)", rows, width);
+    std::string h = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape + ", }";
+    while ((10 + h.size() + 1) % 64 != 0) h += ' ';
+    h += '\n';
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return 1;
+    const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(h.size() & 0xFF),
+                                    (unsigned char)(h.size() >> 8)};
+    bool ok = std::fwrite(head, 1, sizeof head, f) == sizeof head && std::fwrite(h.data(), 1, h.size(), f) == h.size();
+    ok = ok && (bytes == 0 || std::fwrite(data, 1, bytes, f) == bytes);
+    ok = (std::fclose(f) == 0) && ok;
+    if (ok) std::printf("[ETAT]: AOV ecrit dans %s\n", path.c_str());
+    return ok ? 0 : 1;
+}
+
+// --aov: the frame's primary-hit buffers from context c (either backend).
+static int write_aov(rt_ctx* c, bool cpu, rt_frame frame, const char* prefix)
+{
+    frame.flags &= ~RT_FLAG_STATS;  // (not accepted by the AOV pass)
+    const int W = frame.width, H = frame.height;
+    const size_t px = (size_t)W * H;
+    std::vector<float> t(px), n(px * 3);
+    std::vector<int32_t> id(px);
+    const rt_aov out{t.data(), id.data(), n.data()};
+    const int rc = cpu ? rt_cpu_render_aov(c, &frame, &out) : rt_render_aov(c, &frame, &out);
+    if (rc) return fail("rt_render_aov", rc, rt_last_error(c));
+    const std::string p(prefix);
+    static_assert(sizeof(float) == 4, "float32 planes");
+    const uint16_t probe = 1;
+    if (*(const unsigned char*)&probe != 1) return fail("--aov", RT_E_UNSUPPORTED, "little-endian hosts only");
+    if (write_npy(p + "_t.npy", "<f4", H, W, 1, t.data(), px * 4)) return fail("fopen", -1, (p + "_t.npy").c_str());
+    if (write_npy(p + "_id.npy", "<i4", H, W, 1, id.data(), px * 4)) return fail("fopen", -1, (p + "_id.npy").c_str());
+    if (write_npy(p + "_n.npy", "<f4", H, W, 3, n.data(), px * 12)) return fail("fopen", -1, (p + "_n.npy").c_str());
     return 0;
 }
 
@@ -303,6 +354,7 @@ int main(int argc, char** argv)
     bool stats = false, bands = false, cpu = false, dev_given = false, g_given = false;
     int gather = -1;  // -1 auto (RCCL for -g > 1 on distinct GPUs), 0 host, 1 RCCL
     const char* out = nullptr;
+    const char* aov = nullptr;
     for (int i = 2; i < argc; ++i) {
         if (argv[i][0] != '-') continue;
         auto next = [&](int& v) {
@@ -320,6 +372,11 @@ int main(int argc, char** argv)
         if (std::strcmp(argv[i], "--ssaa") == 0) {
             ssaa = 0;
             next(ssaa);
+            continue;
+        }
+        if (std::strcmp(argv[i], "--aov") == 0) {
+            if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--aov needs a file prefix");
+            aov = argv[++i];
             continue;
         }
         if (std::strcmp(argv[i], "--threads") == 0) {
@@ -367,6 +424,9 @@ int main(int argc, char** argv)
     if (ssaa > 1 && (gpus != 1 || bands || gather == 1))
         return fail("arguments", RT_E_ARG,
                     "--ssaa renders on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
+    if (aov && (gpus != 1 || bands || gather == 1))
+        return fail("arguments", RT_E_ARG,
+                    "--aov renders on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
     if (((W - 1) & W) || ((H - 1) & H))
         std::fprintf(stderr, "[ATTENTION]: Resolution %dx%d n'est pas une puissance de deux "
                              "(accepted: the render core has no such restriction)\n", W, H);
@@ -401,6 +461,7 @@ int main(int argc, char** argv)
         }
         std::printf("[ETAT]: Termine! --> Temps total de rendu : %.6f secondes (%d frame(s), CPU)\n", total, frames);
         if (out && write_ppm(out, W, H, img)) return fail("fopen", -1, out);
+        if (aov && write_aov(c, true, frame, aov)) return 1;
         rt_destroy(c);
         rt_scene_destroy(scene);
         return 0;
@@ -423,6 +484,7 @@ int main(int argc, char** argv)
         }
         print_done(c, total, frames, 1, 0, stats);
         if (out && write_ppm(out, W, H, img)) return fail("fopen", -1, out);
+        if (aov && write_aov(c, false, frame, aov)) return 1;
         rt_destroy(c);
         rt_scene_destroy(scene);
         return 0;
@@ -491,6 +553,7 @@ int main(int argc, char** argv)
     }
     print_done(ctx[0], total, frames, gpus, band, stats);
     if (out && write_ppm(out, W, H, full)) return fail("fopen", -1, out);
+    if (aov && write_aov(ctx[0], false, frame, aov)) return 1;
     for (rt_ctx* c : ctx) rt_destroy(c);
     rt_scene_destroy(scene);
     return 0;

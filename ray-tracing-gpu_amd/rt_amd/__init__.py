@@ -23,7 +23,7 @@ from typing import Optional
 import numpy as np
 
 __all__ = [
-    "RtError", "SceneFlat", "Frame", "Stats", "Scene", "Context", "CpuContext", "CScene", "lib", "band_rows",
+    "RtError", "SceneFlat", "Frame", "Stats", "Aov", "Scene", "Context", "CpuContext", "CScene", "lib", "band_rows",
     "frame_rows", "ss_rows", "SS_OPTIONS", "LB_OPTIONS",
     "LIB_PATH", "TRIANGLE", "PLANE", "QUADRIC", "FLAG_STATS", "OPTIONS", "camera_path",
 ]
@@ -89,6 +89,11 @@ class Stats(ctypes.Structure):
         return self.kernel_name.decode()
 
 
+class Aov(ctypes.Structure):
+    """rt.h rt_aov: the requested primary-hit planes (a null pointer: not requested)."""
+    _fields_ = [("t", ctypes.c_void_p), ("id", ctypes.c_void_p), ("n", ctypes.c_void_p)]
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 # Every symbol include/rt.h declares, with its ctypes signature.
@@ -117,6 +122,9 @@ SIGNATURES = {
     "rt_cpu_render_ss": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.c_int32, _VP]),
     "rt_cpu_render_ss_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.c_int32, _VP]),
     "rt_ss_rows": (ctypes.c_int32, [ctypes.POINTER(Frame), ctypes.c_int32]),
+    "rt_render_aov": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Aov)]),
+    "rt_render_aov_async": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Aov), _VP]),
+    "rt_cpu_render_aov": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Aov)]),
     "rt_upload_scene": (ctypes.c_int, [_VP, ctypes.POINTER(SceneFlat)]),
     "rt_render": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
     "rt_render_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
@@ -157,6 +165,20 @@ def ss_rows(frame: "Frame", s: int) -> int:
         raise ValueError("bad supersampling: s in 1..8 must divide the sample frame's width, height and slab rows "
                          "(band_rows: a multiple of 16 s)")
     return rows
+
+
+def _aov_planes(frame: "Frame", t: bool, id: bool, n: bool):
+    """Host arrays for the requested AOV planes and the rt_aov that points at them."""
+    rows, w = frame_rows(frame), frame.width
+    out = {}
+    if t:
+        out["t"] = np.zeros((rows, w), np.float32)
+    if id:
+        out["id"] = np.zeros((rows, w), np.int32)
+    if n:
+        out["n"] = np.zeros((rows, w, 3), np.float32)
+    aov = Aov(*(out[k].ctypes.data if k in out else None for k in ("t", "id", "n")))
+    return out, aov
 
 
 def _option(name) -> int:
@@ -335,6 +357,22 @@ class Context:
         _check("rt_render_ss_async", lib().rt_render_ss_async(self._h, ctypes.byref(frame), s, rgba_dev_ptr or None,
                                                               rgb_dev_ptr or None, stream or None), self._err)
 
+    def render_aov(self, frame: Frame, t: bool = True, id: bool = True, n: bool = True) -> dict:
+        """rt_render_aov: the primary hit of every pixel, no shading.  Returns
+        the requested planes: "t" (rows, W) float32, "id" (rows, W) int32 (file
+        index), "n" (rows, W, 3) float32; a miss is -1, -1, (0, 0, 0); row 0 =
+        bottom, packed like render_float."""
+        out, aov = _aov_planes(frame, t, id, n)
+        _check("rt_render_aov", lib().rt_render_aov(self._h, ctypes.byref(frame), ctypes.byref(aov)), self._err)
+        return out
+
+    def render_aov_async(self, frame: Frame, t_dev_ptr: int = 0, id_dev_ptr: int = 0, n_dev_ptr: int = 0,
+                         stream: int = 0):
+        """rt_render_aov_async: device pointers to the planes (0: not requested), enqueued on `stream`."""
+        aov = Aov(t_dev_ptr or None, id_dev_ptr or None, n_dev_ptr or None)
+        _check("rt_render_aov_async",
+               lib().rt_render_aov_async(self._h, ctypes.byref(frame), ctypes.byref(aov), stream or None), self._err)
+
     def stats(self) -> Stats:
         s = Stats()
         _check("rt_last_stats", lib().rt_last_stats(self._h, ctypes.byref(s)))
@@ -411,6 +449,13 @@ class CpuContext:
         out = np.zeros((ss_rows(frame, s), frame.width // s, 3), np.float32)
         _check("rt_cpu_render_ss_float",
                lib().rt_cpu_render_ss_float(self._h, ctypes.byref(frame), s, out.ctypes.data), self._err)
+        return out
+
+    def render_aov(self, frame: Frame, t: bool = True, id: bool = True, n: bool = True) -> dict:
+        """rt_cpu_render_aov: as Context.render_aov, on host threads (the same bits)."""
+        out, aov = _aov_planes(frame, t, id, n)
+        _check("rt_cpu_render_aov", lib().rt_cpu_render_aov(self._h, ctypes.byref(frame), ctypes.byref(aov)),
+               self._err)
         return out
 
     def stats(self) -> Stats:
@@ -501,3 +546,10 @@ class CScene:
         """m_InfoPixel equivalent: float32 (H, W, 3), unclamped."""
         f = self._frame()
         return self._ctx.render_float(f) if self._ss == 1 else self._ctx.render_ss_float(f, self._ss)
+
+    def LancerRayonsAOV(self) -> dict:
+        """The primary-hit buffers of the frame LancerRayons renders (not in
+        the reference): {"t", "id", "n"} as Context.render_aov returns them.
+        With supersampling they are those of the s W x s H sample grid."""
+        f = self._frame()
+        return self._ctx.render_aov(f)
