@@ -111,6 +111,15 @@ int rt_debug_lb_offsets(rt_ctx*, int light, unsigned* out, int n);
  * entry]. */
 int rt_debug_lb_region_build(const unsigned* off, int R, double* out5);
 
+/* The row chunks a render enqueues, no device: a frame of `rows` packed rows
+ * (sample rows when ss > 1) of `width` pixels, px_bytes of output per pixel;
+ * wf: it renders as a wavefront; host_out: a synchronous render into host
+ * memory; the options RT_OPT_HOST_CHUNK_MB and RT_OPT_SS_CHUNK_ROWS.  Writes
+ * the n + 1 boundaries bounds[0] = 0 < ... < bounds[n] = rows (cap: the
+ * array's length) and returns n, or RT_E_ARG. */
+int rt_debug_row_chunks(int width, int rows, int band_rows, int px_bytes, int ss, int wf, int host_out,
+                        double host_chunk_mb, double ss_chunk_rows, int* bounds, int cap);
+
 #ifdef RT_PROF
 /* Only in a library built with -DRT_PROF (tools/prof_sections.py,
  * tools/prof_tiles.py): per-section shader-clock totals and event counts

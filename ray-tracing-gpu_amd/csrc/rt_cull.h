@@ -6,6 +6,8 @@
 #ifndef RT_AMD_RT_CULL_H
 #define RT_AMD_RT_CULL_H
 
+#include <cstring>
+
 #include "rt_primitives.h"
 
 #pragma clang fp contract(off)
@@ -23,9 +25,7 @@ namespace rt {
 // per triangle — and only the ballot's survivors are tested exactly.  The
 // per-lane predicates above remain the definition; the margins here only
 // widen them (cos W lowered, sin W raised, cos(W + T) lowered by 2e-6 and by
-// the shadow ray's direction slack).
-__device__ __forceinline__ bool wave_full() { return __builtin_amdgcn_read_exec() == ~0ull; }
-
+// the shadow ray's direction slack).  (wave_full: rt_layout.h.)
 template <int CTRL>
 __device__ __forceinline__ float dppf(float v)
 {
@@ -52,18 +52,6 @@ __device__ __forceinline__ float wave_max(float v)
     v = fmaxf(v, dppf<0x141>(v));
     v = fmaxf(v, dppf<0x140>(v));
     return fmaxf(fmaxf(readlanef(v, 0), readlanef(v, 16)), fmaxf(readlanef(v, 32), readlanef(v, 48)));
-}
-// Sum over all 64 lanes (full exec only), for the stats tallies.
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-    // the stats launch is untimed: 64 scalar reads are simple and exact
-    unsigned long long t = 0;
-    for (int l = 0; l < 64; ++l) {
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-        t += ((unsigned long long)hi << 32) | lo;
-    }
-    return t;
 }
 
 struct WaveCone {
@@ -502,6 +490,43 @@ struct TinyLaunch {
     // per triangle, nearest first: TinyCam's records
     float4 rec[8 * kTinyMax];
 };
+// The header of one launch (host side; rt_trace_tiny unpacks it): the
+// frame's, the scene's and the camera records' wave-uniform values.
+// h_plane: the host copy of plane[] ([n cst] [file index 0 0 0] per plane);
+// lrec: the light records' set the launch shades with.
+inline void tiny_head_fill(TinyHead& H, const FrameDev& F, const SceneDev& S, const TinyCam& T, const float* h_plane,
+                           const float4* lrec, unsigned* rgba, float* rgbf, StatsDev* stats)
+{
+    H = TinyHead{};
+    std::memcpy(H.cam, F.cam, sizeof H.cam);
+    H.width = F.width;
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 3; ++j) H.orient[3 * i + j] = F.orient[4 * i + j];
+    H.half_w = F.half_w, H.half_h = F.half_h, H.inv_w = F.inv_w, H.inv_h = F.inv_h;
+    std::memcpy(H.bg, F.bg, sizeof H.bg);
+    H.height = F.height;
+    H.row_begin = F.row_begin, H.row_end = F.row_end;
+    H.band_rows = F.band_rows, H.band_count = F.band_count, H.band_index = F.band_index;
+    H.flags = F.flags;
+    H.n = T.n, H.masked = T.masked, H.mask = T.mask, H.tiles_x = T.tiles_x;
+    H.n_plane = S.n_plane;
+    // the planes' camera-ray constants, hit_plane's n . O + cst in float
+    // (this file is built without contraction, host and device)
+    const Vec3 O = make3(F.cam[0], F.cam[1], F.cam[2]);
+    for (int k = 0; k < kTinyPlanes && k < S.n_plane; ++k) {
+        const float* p = &h_plane[8 * (size_t)k];
+        H.plane[k] = make_float4(p[0], p[1], p[2], p[3]);
+        H.pnum[k] = dot(make3(p[0], p[1], p[2]), O) + p[3];
+        std::memcpy(&H.pidx[k], &p[4], sizeof(int));
+    }
+    H.rgba = rgba, H.rgbf = rgbf, H.stats = stats;
+    H.geom = S.geom, H.mat = S.mat, H.lrec = lrec, H.planes = S.plane, H.quad = S.quad;
+    H.translucent = S.translucent;
+    H.lb_off = S.lb_off, H.lb_ent = S.lb_ent, H.lb_dcap = S.lb_dcap, H.cone_light = S.cone_light, H.tri = S.tri;
+    H.n_lights = S.n_lights, H.n_tri = S.n_tri, H.n_tri_opaque = S.n_tri_opaque;
+    H.n_plane_opaque = S.n_plane_opaque, H.n_quad = S.n_quad, H.n_quad_opaque = S.n_quad_opaque;
+    H.n_translucent = S.n_translucent, H.shadow_split = S.shadow_split;
+}
 
 // The tile's mask, computed by the wave: lane j < n tests triangle j against
 // the tile cone around lane 36's direction (full wave: depth-0 kernels run

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cstdlib>
 #include <cmath>
@@ -39,6 +40,7 @@
 
 #include "../../include/rt.h"
 #include "../../include/rt_debug.h"
+#include "rt_chunks.h"
 #include "rt_cpu.hpp"
 #include "rt_scan.h"
 #include "rt_shade.h"
@@ -362,45 +364,10 @@ __device__ __forceinline__ void trace_tile(const SceneDev& S, const FrameDev& F,
             }
         }
     }
-#ifdef RT_PROF
-    RT_MARK(cnt, 6);
-    if ((threadIdx.x & 63) == 0) {
-        unsigned long long tot = 0;
-        for (int i = 0; i < 8; ++i) {
-            atomicAdd(&rt_prof_acc[i], cnt.pt[i]);
-            atomicAdd(&rt_prof_ev[i], (unsigned long long)cnt.ev[i]);
-            tot += cnt.pt[i];
-        }
-        const int tile = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-        if (rt_prof_tiles && tile < rt_prof_ntiles) {
-            unsigned* o = rt_prof_tiles + 16 * (size_t)tile;
-            o[0] = (unsigned)tot;
-            o[1] = (unsigned)(tot >> 32);
-            for (int i = 0; i < 8; ++i) o[2 + i] = (unsigned)(cnt.pt[i] >> 8);
-            const int evi[6] = {1, 2, 4, 5, 6, 7};  // cam member batches, cam exact, shadow member
-            for (int i = 0; i < 6; ++i) o[10 + i] = cnt.ev[evi[i]];  // batches, exact, by dcap, by cone
-        }
-    }
-#endif
+    tile_prof_flush(cnt);
     // Only the COUNT variant (the RT_FLAG_STATS launch, pick_kernel) tallies:
     // in the timed kernels every counter is dead code.
-    if (COUNT && (F.flags & RT_FLAG_STATS)) {
-        unsigned long long v[9] = {cnt.primary, cnt.bounce, cnt.shadow, cnt.skipped, cnt.tri,
-                                   cnt.pla,     cnt.qua,    cnt.btri,   cnt.bnode};
-        StatsDev* sl = stats + ((blockIdx.x + blockIdx.y * gridDim.x) % kStatSlots);
-        unsigned long long* dst[9] = {&sl->primary, &sl->bounce, &sl->shadow, &sl->skipped, &sl->tri,
-                                      &sl->pla,     &sl->qua,    &sl->btri,   &sl->bnode};
-        if (wave_full()) {  // one atomic per counter per wave
-#pragma unroll
-            for (int i = 0; i < 9; ++i) {
-                const unsigned long long w = wave_sum_u64(v[i]);
-                if ((threadIdx.x & 63) == 0) atomicAdd(dst[i], w);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) atomicAdd(dst[i], v[i]);
-        }
-    }
+    if (COUNT && (F.flags & RT_FLAG_STATS)) tile_tally(cnt, stats, false);
 }
 
 // One wave per workgroup: one 8 x 8 tile each, so a CU takes a new tile as
@@ -626,38 +593,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     // completion held up the loads behind it (A/B: C2 -2.8%, C4 -2.5%)
     if constexpr ((WAVE & 128) != 0)
         if (lane == 0 && tiled) mask[tile] = tmask;
-#ifdef RT_PROF
-    RT_MARK(cnt, 6);
-    if (lane == 0) {  // the section clocks and per-tile record, as trace_tile
-        unsigned long long tot = 0;
-        for (int i = 0; i < 8; ++i) {
-            atomicAdd(&rt_prof_acc[i], cnt.pt[i]);
-            atomicAdd(&rt_prof_ev[i], (unsigned long long)cnt.ev[i]);
-            tot += cnt.pt[i];
-        }
-        const int ptile = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-        if (rt_prof_tiles && ptile < rt_prof_ntiles) {
-            unsigned* o = rt_prof_tiles + 16 * (size_t)ptile;
-            o[0] = (unsigned)tot;
-            o[1] = (unsigned)(tot >> 32);
-            for (int i = 0; i < 8; ++i) o[2 + i] = (unsigned)(cnt.pt[i] >> 8);
-            const int evi[6] = {1, 2, 4, 5, 6, 7};
-            for (int i = 0; i < 6; ++i) o[10 + i] = cnt.ev[evi[i]];
-        }
-    }
-#endif
-    if (COUNT && (F.flags & RT_FLAG_STATS)) {  // the RT_FLAG_STATS launch's tallies (trace_tile)
-        unsigned long long v[9] = {cnt.primary, cnt.bounce, cnt.shadow, cnt.skipped, cnt.tri,
-                                   cnt.pla,     cnt.qua,    cnt.btri,   cnt.bnode};
-        StatsDev* sl = H.stats + ((blockIdx.x + blockIdx.y * gridDim.x) % kStatSlots);
-        unsigned long long* dst[9] = {&sl->primary, &sl->bounce, &sl->shadow, &sl->skipped, &sl->tri,
-                                      &sl->pla,     &sl->qua,    &sl->btri,   &sl->bnode};
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {  // one atomic per counter per wave (every lane runs)
-            const unsigned long long w = wave_sum_u64(v[i]);
-            if (lane == 0) atomicAdd(dst[i], w);
-        }
-    }
+    tile_prof_flush(cnt);
+    if (COUNT && (F.flags & RT_FLAG_STATS)) tile_tally(cnt, H.stats, true);  // (every lane runs)
 }
 
 // Compiled bounce-stack capacities.  The host picks the smallest one that
@@ -1099,19 +1036,25 @@ static void free_deferred(rt_ctx* c)
     c->deferred.clear();
 }
 
-// Host sync of everything the context enqueued: afterwards no async render
-// or state write is in flight.
-static int sync_all(rt_ctx* c)
+// The context after a host sync of everything it enqueued: no async render,
+// state write, wavefront frame or resolve is in flight any more.
+static void settled(rt_ctx* c)
 {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-    for (hipStream_t s : c->async_streams) HIP_TRY(c, hipStreamSynchronize(s));
     c->async_streams.clear();
     c->state_pending = false;
     c->state_stream = nullptr;
     c->wf.pending = false;
     c->ss.pending = false;
     free_deferred(c);
+}
+
+// Host sync of everything the context enqueued.
+static int sync_all(rt_ctx* c)
+{
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+    for (hipStream_t s : c->async_streams) HIP_TRY(c, hipStreamSynchronize(s));
+    settled(c);
     return RT_OK;
 }
 
@@ -2337,13 +2280,14 @@ static void trace_dims(int width, int rows, dim3& grid, dim3& block)
 // The launch-camera kernel (tiny scenes: camera buffer replaced by the
 // launch's records, light-buffer shadows, one light per pass); SELF: the
 // camera's first frame on the stream, which computes and stores the masks.
-template <bool COUNT>
-static const void* tiny_kernel(int mode)
-{
-    return mode == 2   ? (const void*)&rt_trace_tiny<0, 1, 229, COUNT>
-           : mode == 1 ? (const void*)&rt_trace_tiny<0, 1, 101, COUNT>
-                       : (const void*)&rt_trace_tiny<0, 1, 37, COUNT>;
-}
+// By tile-mask mode (tiny_masks): its WAVE value and kernels, k[COUNT].
+struct TinyKernel {
+    int wave;
+    const void* k[2];
+};
+#define RT_TINY(W) {W, {(const void*)&rt_trace_tiny<0, 1, W, false>, (const void*)&rt_trace_tiny<0, 1, W, true>}}
+static const TinyKernel kTinyKernels[3] = {RT_TINY(37), RT_TINY(101), RT_TINY(229)};
+#undef RT_TINY
 
 // The launch grid over `rows` output rows and the frame's tile-dealing fields
 // (tile_of_block); big: a big-list kernel (WAVE bit 2), whose RT_OPT_XCD_DEAL
@@ -2384,39 +2328,11 @@ static int launch_trace(rt_ctx* c, const KernelPick& kp, const TinyCam* T, bool 
         // the launch record (rt_cull.h TinyLaunch): the frame's, the scene's
         // and the camera records' wave-uniform values, one argument
         TinyLaunch Lr;
-        TinyHead& H = Lr.h;
-        H = TinyHead{};
-        std::memcpy(H.cam, F.cam, sizeof H.cam);
-        H.width = F.width;
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 3; ++j) H.orient[3 * i + j] = F.orient[4 * i + j];
-        H.half_w = F.half_w, H.half_h = F.half_h, H.inv_w = F.inv_w, H.inv_h = F.inv_h;
-        std::memcpy(H.bg, F.bg, sizeof H.bg);
-        H.height = F.height;
-        H.row_begin = F.row_begin, H.row_end = F.row_end;
-        H.band_rows = F.band_rows, H.band_count = F.band_count, H.band_index = F.band_index;
-        H.flags = F.flags;
-        H.n = T->n, H.masked = T->masked, H.mask = T->mask, H.tiles_x = T->tiles_x;
-        H.n_plane = S.n_plane;
-        // the planes' camera-ray constants, hit_plane's n . O + cst in float
-        // (this file is built without contraction, host and device)
-        const Vec3 O = make3(F.cam[0], F.cam[1], F.cam[2]);
-        for (int k = 0; k < kTinyPlanes && k < S.n_plane; ++k) {
-            const float* p = &c->h_plane[8 * (size_t)k];
-            H.plane[k] = make_float4(p[0], p[1], p[2], p[3]);
-            H.pnum[k] = dot(make3(p[0], p[1], p[2]), O) + p[3];
-            std::memcpy(&H.pidx[k], &p[4], sizeof(int));
-        }
-        H.rgba = oa, H.rgbf = ob, H.stats = stats;
-        H.geom = S.geom, H.mat = S.mat, H.lrec = c->d_lrec + (c->opt_lb_region ? 0 : kLightRec * S.n_lights), H.planes = S.plane, H.quad = S.quad;
-        H.translucent = S.translucent;
-        H.lb_off = S.lb_off, H.lb_ent = S.lb_ent, H.lb_dcap = S.lb_dcap, H.cone_light = S.cone_light, H.tri = S.tri;
-        H.n_lights = S.n_lights, H.n_tri = S.n_tri, H.n_tri_opaque = S.n_tri_opaque;
-        H.n_plane_opaque = S.n_plane_opaque, H.n_quad = S.n_quad, H.n_quad_opaque = S.n_quad_opaque;
-        H.n_translucent = S.n_translucent, H.shadow_split = S.shadow_split;
+        tiny_head_fill(Lr.h, F, S, *T, c->h_plane.data(),
+                       c->d_lrec + (c->opt_lb_region ? 0 : kLightRec * S.n_lights), oa, ob, stats);
         std::memcpy(Lr.rec, T->rec, sizeof Lr.rec);
         void* args[] = {&Lr};
-        HIP_TRY(c, hipLaunchKernel(count ? tiny_kernel<true>(mode) : tiny_kernel<false>(mode), grid, block, args, 0, st));
+        HIP_TRY(c, hipLaunchKernel(kTinyKernels[mode].k[count], grid, block, args, 0, st));
         return RT_OK;
     }
     void* args[] = {&S, &F, &oa, &ob, &stats};
@@ -2620,13 +2536,6 @@ static int prepare_state(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync
     return RT_OK;
 }
 
-// sync_path: rt_render / rt_render_float on c->stream; else rt_render_async
-// on the caller's stream (both build the camera buffer when it is not current).
-// host_out (synchronous renders into host memory): the output is copied
-// there — for a big slab in up to 8 row chunks (multiples of 16 rows, one
-// per RT_OPT_HOST_CHUNK_MB of output), chunk i's copy on c->copy_stream
-// overlapping chunk i + 1's kernel (the same pixels: every pixel is independent, and the chunks keep
-// the unchunked launch's 8-row wave rows).
 // ---- wavefront bounce levels (rt_wavefront.h)
 // Children one node can spawn (the gates compare K * energy > min_energy,
 // Scene.cpp:1780,1791): with min_energy >= 0 a reflected ray needs some
@@ -2984,28 +2893,6 @@ static int ss_valid_rows(const rt_frame* f, int rows)
     return v;
 }
 
-// Sample rows per chunk of a supersampled slab frame (RT_OPT_SS_CHUNK_ROWS
-// output rows, a multiple of 16, times s; so every chunk starts on a multiple
-// of 16 s sample rows of the slab: the 8-row tiles of the camera buffer stay
-// aligned).  Auto: the fewest equal chunks whose float samples stay within
-// 224 MiB each — under the 256 MiB Infinity Cache, so the resolve still finds
-// them there.  Measured (tools/ssaa_probe.py): every chunk more
-// costs 12 us (C2) to 50 us (C3) of drained GPU at 3840 x 2160 samples, where
-// one chunk (95 MiB) is fastest; at 7680 x 4320 (380 MiB) two chunks beat one
-// by 1.4% and four lose 2.4%.
-static int ss_chunk_sample_rows(const rt_ctx* c, const rt_frame* f, int rows, int s)
-{
-    const double row_bytes = (double)f->width * 12.0;
-    double ch = c->opt_ss_chunk_rows;
-    if (ch == 0) {
-        const double n = std::ceil(row_bytes * rows / (224.0 * 1048576.0));
-        if (n <= 1) return rows;
-        ch = std::ceil((double)(rows / s) / n);
-    }
-    ch = std::max(16.0, std::ceil(ch / 16.0) * 16.0);
-    return (int)std::min((double)rows, ch * s);
-}
-
 template <int S>
 static const void* resolve_kernel(bool vec)
 {
@@ -3037,45 +2924,78 @@ static int launch_resolve(rt_ctx* c, const float* samples, int width, int s, int
     return RT_OK;
 }
 
-// ss > 1: a supersampled render — rgba_dev / rgb_dev take the resolved
-// width / ss x rows / ss image (no host_out); the samples go to c->ss.
-static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_dev, hipStream_t st, bool timed,
-                  bool sync_path, void* host_out = nullptr, int ss = 1)
+// ---- entry checks: each sets the error string and returns the code, or RT_OK
+// (every entry point keeps its own order of them)
+static int needs_cpu(rt_ctx* c, const char* entry)
 {
-    if (!c || !f) return RT_E_ARG;
-    if (!c->uploaded) {
-        c->err = "render before rt_upload_scene";
-        return RT_E_STATE;
-    }
-    if (!frame_ok(f)) {
-        c->err = "bad rt_frame geometry";
-        return RT_E_ARG;
-    }
-    bool capturing = false;
-    if (!sync_path) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIP_TRY(c, hipStreamIsCapturing(st, &cs));
-        capturing = cs != hipStreamCaptureStatusNone;
-    }
-    const int depth = reachable_depth(c, f);
-    const bool lbuf = lbuf_on(c);
-    const bool bvh = bvh_on(c, depth, lbuf);
+    c->err = std::string(entry) + " needs a CPU context (rt_create_cpu)";
+    return RT_E_STATE;
+}
+static int check_uploaded(rt_ctx* c, const char* what = "render")
+{
+    if (c->uploaded) return RT_OK;
+    c->err = std::string(what) + " before rt_upload_scene";
+    return RT_E_STATE;
+}
+static int check_frame(rt_ctx* c, const rt_frame* f)
+{
+    if (frame_ok(f)) return RT_OK;
+    c->err = "bad rt_frame geometry";
+    return RT_E_ARG;
+}
+// Is st being captured into a hipGraph?
+static int stream_capturing(rt_ctx* c, hipStream_t st, bool* capturing)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(c, hipStreamIsCapturing(st, &cs));
+    *capturing = cs != hipStreamCaptureStatusNone;
+    return RT_OK;
+}
+
+// ---- a colour frame: plan_frame decides, launch enqueues what was decided.
+// The plan of one frame: its kernel and that kernel's arguments, and its
+// packed rows as chunks [r0, r0 + step) — step == rows: one chunk
+// (rt_chunks.h).  A new render mode is a field here and a step of launch's
+// loop, not another copy of the loop.
+struct FramePlan {
+    int depth, rows, step;
+    int tmode;  // tiny: the tile masks, 0 read, 1 computed by the kernel, 2 computed and stored (tiny_masks)
+    bool lbuf, bvh, cbuf, wf;
+    bool tiny;       // the launch-camera kernel (T: its records, no device state)
+    bool ss_staged;  // supersampled: the chunks render into c->ss and are resolved from there
+    KernelPick kp;
+    TinyCam T;
+    SceneDev S;
+    FrameDev F;
+};
+
+// Plans frame f for stream st, into P (filled in place: TinyCam and SceneDev
+// are large).  What the plan needs on the device is enqueued or allocated
+// here: the tile masks' buffer, the per-camera state, the wavefront queues,
+// the sample intermediate.  Fills c->last.
+// ss > 1: a supersampled render — the samples go to c->ss, one chunk at a
+// time; px_bytes, host_out: the output's bytes per pixel and whether launch
+// copies it to the host (rt_chunks.h).
+static int plan_frame(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync_path, bool capturing, int px_bytes,
+                      bool host_out, int ss, FramePlan& P)
+{
+    const int depth = P.depth = reachable_depth(c, f);
+    const bool lbuf = P.lbuf = lbuf_on(c);
+    const bool bvh = P.bvh = bvh_on(c, depth, lbuf);
     const bool cb_want = cam_lists(c, depth, lbuf) && c->n_tri > 0 && c->opt_camera_buffer && cb_frame_ok(f);
-    const int rows = frame_rows(f);
+    const int rows = P.rows = frame_rows(f);
     // tiny scenes: the camera records travel with the launch (no device state)
-    TinyCam Tl;
-    const TinyCam* tiny = nullptr;
-    int tmode = 0;  // the tile masks: 0 read, 1 computed by the kernel, 2 computed and stored (tiny_masks)
-    if (tiny_ok(c, depth, lbuf)) {
-        Tl = tiny_prepare(c, f);
+    P.tmode = 0;
+    P.tiny = tiny_ok(c, depth, lbuf);
+    if (P.tiny) {
+        P.T = tiny_prepare(c, f);
         if (rows > 0)
-            if (int rc = tiny_masks(c, f, st, capturing, Tl, &tmode)) return rc;
-        tiny = &Tl;
+            if (int rc = tiny_masks(c, f, st, capturing, P.T, &P.tmode)) return rc;
     }
-    if (rows > 0 && !tiny) {
+    if (rows > 0 && !P.tiny) {
         if (int rc = prepare_state(c, f, st, sync_path, capturing, cb_want)) return rc;
     }
-    const bool cbuf = !tiny && cb_want && cb_matches(c->cb, f);
+    const bool cbuf = P.cbuf = !P.tiny && cb_want && cb_matches(c->cb, f);
     // Wavefront: a BVH frame's bounce levels as compacted queues (rt_wavefront.h);
     // its queues are shared by the context's streams: a frame on another
     // stream than the last wavefront frame waits for that one.  A captured
@@ -3086,13 +3006,18 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
         if (int rc = wf_ensure(c, f, rows, depth, capturing, &ok)) return rc;
         wf = ok;
     }
+    P.wf = wf;
     // A supersampled frame's samples: slabs that are not wavefronts in row
     // chunks (the intermediate holds one chunk), everything else whole.
-    int ss_step = rows;
-    if (ss > 1 && rows > 0) {
-        if (!wf && f->band_rows == 0) ss_step = ss_chunk_sample_rows(c, f, rows, ss);
+    P.ss_staged = ss > 1;
+    P.step = row_chunk_step(f->width, rows, f->band_rows, px_bytes, ss, wf, host_out, c->opt_host_chunk_mb,
+                            c->opt_ss_chunk_rows);
+    // tiny is depth 0, a wavefront BVH depth above 0; a wavefront is one
+    // chunk; a supersampled call's caller copies the resolved image itself
+    assert(!(P.tiny && wf) && (!wf || P.step == rows) && !(P.ss_staged && host_out));
+    if (P.ss_staged && rows > 0) {
         rt_ctx::SsBuf& B = c->ss;
-        const size_t need = (size_t)ss_step * f->width * 12;
+        const size_t need = (size_t)P.step * f->width * 12;
         if (need > B.bytes) {
             if (capturing) {
                 c->err = "rt_render_ss_async in a capture: the sample intermediate is not sized (render the frame "
@@ -3109,118 +3034,112 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
     }
     const bool count = (f->flags & RT_FLAG_STATS) != 0;
     const bool small = (double)f->width * rows < 4e6 && c->opt_lb_unroll;
-    const KernelPick kp = wf ? (count ? pick_wf0<true>(c->n_tri, cbuf, small) : pick_wf0<false>(c->n_tri, cbuf, small))
-                             : (count ? pick_kernel<true>(depth, c->n_tri, c->n_lights, lbuf, cbuf,
-                                                          bvh ? c->bvh_depth : 0, reflect_chain(c, f), small)
-                                      : pick_kernel<false>(depth, c->n_tri, c->n_lights, lbuf, cbuf,
-                                                           bvh ? c->bvh_depth : 0, reflect_chain(c, f), small));
+    P.kp = wf ? (count ? pick_wf0<true>(c->n_tri, cbuf, small) : pick_wf0<false>(c->n_tri, cbuf, small))
+              : (count ? pick_kernel<true>(depth, c->n_tri, c->n_lights, lbuf, cbuf, bvh ? c->bvh_depth : 0,
+                                           reflect_chain(c, f), small)
+                       : pick_kernel<false>(depth, c->n_tri, c->n_lights, lbuf, cbuf, bvh ? c->bvh_depth : 0,
+                                            reflect_chain(c, f), small));
+    const KernelPick& kp = P.kp;
     if (!kp.k) {
         c->err = "reachable bounce depth " + std::to_string(depth) + " exceeds the compiled stack (32)";
         return RT_E_UNSUPPORTED;
     }
-    SceneDev S = scene_dev(c, lbuf, cbuf);
-    FrameDev F;
-    frame_dev(f, F);
-    if (wf) F.wf = c->wf.dev;
+    P.S = scene_dev(c, lbuf, cbuf);
+    frame_dev(f, P.F);
+    if (wf) P.F.wf = c->wf.dev;
     c->last = rt_stats{};
     c->last.stack_depth = wf ? depth : kp.cap;
     c->last.light_batch = kp.lb;
     if (wf)
         std::snprintf(c->last.kernel, sizeof c->last.kernel, "wavefront %s + %d levels", kp.name, depth);
-    else if (tiny)
-        std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_trace_tiny<0,1,%d>",
-                      tmode == 2 ? 229 : (tmode == 1 ? 101 : 37));
+    else if (P.tiny)
+        std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_trace_tiny<0,1,%d>", kTinyKernels[P.tmode].wave);
     else
         std::memcpy(c->last.kernel, kp.name, sizeof kp.name);
+    return RT_OK;
+}
+
+// One colour frame on st.  sync_path: rt_render / rt_render_float /
+// rt_render_ss* on c->stream; else rt_render_async / rt_render_ss_async on
+// the caller's stream (both build the camera buffer when it is not current).
+// rgba_dev / rgb_dev take the image (ss > 1: the resolved width / ss x
+// rows / ss one).  host_out (synchronous renders into host memory, ss == 1):
+// the image is copied there, one copy on st, or — a slab in chunks — chunk
+// i's copy on c->copy_stream overlapping chunk i + 1's kernel.
+static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_dev, hipStream_t st, bool timed,
+                  bool sync_path, void* host_out = nullptr, int ss = 1)
+{
+    if (!c || !f) return RT_E_ARG;
+    if (int rc = check_uploaded(c)) return rc;
+    if (int rc = check_frame(c, f)) return rc;
+    bool capturing = false;
+    if (!sync_path)
+        if (int rc = stream_capturing(c, st, &capturing)) return rc;
+    const size_t px_bytes = rgba_dev ? 4 : 12;
+    FramePlan P;
+    if (int rc = plan_frame(c, f, st, sync_path, capturing, (int)px_bytes, host_out != nullptr, ss, P)) return rc;
+    const int rows = P.rows, step = P.step;
     if (rows == 0) return RT_OK;
-    if (f->flags & RT_FLAG_STATS) HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, kStatSlots * sizeof(StatsDev), st));
+    const bool count = (f->flags & RT_FLAG_STATS) != 0;
+    if (count) HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, kStatSlots * sizeof(StatsDev), st));
     if (timed) HIP_TRY(c, hipEventRecord(c->ev0, st));
     StatsDev* stats = c->d_stats;
-    const size_t px_bytes = rgba_dev ? 4 : 12;
-    // a chunk per RT_OPT_HOST_CHUNK_MB (8 MiB; each copy has a fixed cost of
-    // tens of us: a 1080p RGBA8 frame is one copy, 4K four chunks -10%,
-    // 7680 x 4320 eight chunks -30%, tools/host_chunks.py)
-    const size_t out_bytes = (size_t)rows * f->width * px_bytes;
-    const double chunk = c->opt_host_chunk_mb * 1048576.0;
-    const int nch = (host_out && f->band_rows == 0 && chunk > 0 && !wf)
-                        ? (int)std::min(8.0, std::floor((double)out_bytes / chunk))
-                        : 1;
-    if (wf) {
+    if (P.wf) {
         rt_ctx::WfBuf& W = c->wf;
         if (W.pending && W.last != st) HIP_TRY(c, hipStreamWaitEvent(st, W.ev, 0));
         HIP_TRY(c, hipMemsetAsync(W.dev.count, 0, kWfCountBytes, st));
         if (W.sort)  // the bin counts (level 1's: the level-0 kernel's appends)
             HIP_TRY(c, hipMemsetAsync(W.dev.hist, 0, 2 * W.hcap * sizeof(unsigned), st));
     }
-    if (ss > 1) {
-        rt_ctx::SsBuf& B = c->ss;
-        if (B.pending && B.last != st && !capturing) HIP_TRY(c, hipStreamWaitEvent(st, B.ev, 0));
-        const int wo = f->width / ss;
-        const int vrows = ss_valid_rows(f, rows);
-        for (int r0 = 0; r0 < rows; r0 += ss_step) {
-            const int r1 = std::min(rows, r0 + ss_step);
-            FrameDev Fc = F;
-            if (ss_step < rows) {
-                Fc.row_begin = f->row_begin + r0;
-                Fc.row_end = f->row_begin + r1;
-            }
-            if (int rc = launch_trace(c, kp, tiny, f->flags & RT_FLAG_STATS, S, Fc, f->width, r1 - r0, nullptr, B.mem,
-                                      stats, st, tmode))
-                return rc;
-            if (wf) {  // (one chunk)
-                if (int rc = wf_levels(c, S, Fc, depth, count, nullptr, B.mem, stats, st)) return rc;
-                HIP_TRY(c, hipEventRecord(c->wf.ev, st));
-                c->wf.last = st;
-                c->wf.pending = true;
-            }
+    rt_ctx::SsBuf& B = c->ss;
+    if (P.ss_staged && B.pending && B.last != st && !capturing) HIP_TRY(c, hipStreamWaitEvent(st, B.ev, 0));
+    // every chunk's kernel first, then the copies (a copy into pageable
+    // memory blocks the host; the kernels behind it keep running)
+    const bool host_chunked = host_out && step < rows;
+    const int wo = f->width / ss, vrows = ss_valid_rows(f, rows);
+    int n = 0;
+    for (int r0 = 0; r0 < rows; r0 += step, ++n) {
+        const int r1 = std::min(rows, r0 + step);
+        FrameDev Fc, *F = &P.F;
+        if (step < rows) {
+            Fc = P.F;
+            Fc.row_begin = f->row_begin + r0;
+            Fc.row_end = f->row_begin + r1;
+            F = &Fc;
+        }
+        unsigned* oa = P.ss_staged ? nullptr : (rgba_dev ? rgba_dev + (size_t)r0 * f->width : nullptr);
+        float* ob = P.ss_staged ? B.mem : (rgb_dev ? rgb_dev + (size_t)r0 * f->width * 3 : nullptr);
+        if (int rc = launch_trace(c, P.kp, P.tiny ? &P.T : nullptr, count, P.S, *F, f->width, r1 - r0, oa, ob, stats, st,
+                                  P.tmode))
+            return rc;
+        if (P.wf) {  // (one chunk)
+            if (int rc = wf_levels(c, P.S, *F, P.depth, count, oa, ob, stats, st)) return rc;
+            HIP_TRY(c, hipEventRecord(c->wf.ev, st));
+            c->wf.last = st;
+            c->wf.pending = true;
+        }
+        if (P.ss_staged) {  // the chunk's rows inside the frame
             const int q0 = r0 / ss, nq = (std::max(r0, std::min(r1, vrows)) - r0) / ss;
             if (int rc = launch_resolve(c, B.mem, f->width, ss, nq, rgb_dev ? rgb_dev + (size_t)q0 * wo * 3 : nullptr,
                                         rgba_dev ? rgba_dev + (size_t)q0 * wo : nullptr, st))
                 return rc;
         }
-        if (tmode == 2)
-            if (int rc = tiny_masks_stored(c, st)) return rc;
-        if (!capturing) {
-            HIP_TRY(c, hipEventRecord(B.ev, st));
-            B.last = st;
-            B.pending = true;
-        }
-    } else if (nch <= 1) {
-        if (int rc = launch_trace(c, kp, tiny, f->flags & RT_FLAG_STATS, S, F, f->width, rows, rgba_dev, rgb_dev, stats,
-                                  st, tmode))
-            return rc;
-        if (tmode == 2)
-            if (int rc = tiny_masks_stored(c, st)) return rc;
-        if (wf) {
-            if (int rc = wf_levels(c, S, F, depth, count, rgba_dev, rgb_dev, stats, st)) return rc;
-            HIP_TRY(c, hipEventRecord(c->wf.ev, st));
-            c->wf.last = st;
-            c->wf.pending = true;
-        }
-        if (host_out)
-            HIP_TRY(c, hipMemcpyAsync(host_out, rgba_dev ? (void*)rgba_dev : (void*)rgb_dev,
-                                      (size_t)rows * f->width * px_bytes, hipMemcpyDeviceToHost, st));
-    } else {
-        // every chunk's kernel first, then the copies (a copy into pageable
-        // memory blocks the host; the kernels behind it keep running)
-        const int step = ((rows + nch - 1) / nch + 15) / 16 * 16;
-        int n = 0;
-        for (int r0 = 0; r0 < rows; r0 += step, ++n) {
-            const int r1 = std::min(rows, r0 + step);
-            FrameDev Fc = F;
-            Fc.row_begin = f->row_begin + r0;
-            Fc.row_end = f->row_begin + r1;
-            unsigned* oa = rgba_dev ? rgba_dev + (size_t)r0 * f->width : nullptr;
-            float* ob = rgb_dev ? rgb_dev + (size_t)r0 * f->width * 3 : nullptr;
-            if (int rc = launch_trace(c, kp, tiny, f->flags & RT_FLAG_STATS, S, Fc, f->width, r1 - r0, oa, ob, stats, st,
-                                      tmode))
-                return rc;
+        if (host_chunked) {
+            assert(n < 8);
             HIP_TRY(c, hipEventRecord(c->ev_chunk[n], st));
         }
-        if (tmode == 2)
-            if (int rc = tiny_masks_stored(c, st)) return rc;
+    }
+    if (P.tmode == 2)
+        if (int rc = tiny_masks_stored(c, st)) return rc;
+    if (P.ss_staged && !capturing) {
+        HIP_TRY(c, hipEventRecord(B.ev, st));
+        B.last = st;
+        B.pending = true;
+    }
+    const char* src = (const char*)(rgba_dev ? (void*)rgba_dev : (void*)rgb_dev);
+    if (host_chunked) {
         if (timed) HIP_TRY(c, hipEventRecord(c->ev1, st));
-        const char* src = (const char*)(rgba_dev ? (void*)rgba_dev : (void*)rgb_dev);
+        timed = false;  // ev1: after the last kernel, before the copies
         for (int i = 0; i < n; ++i) {
             const int r0 = i * step, r1 = std::min(rows, r0 + step);
             const size_t off = (size_t)r0 * f->width * px_bytes;
@@ -3228,12 +3147,13 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
             HIP_TRY(c, hipMemcpyAsync((char*)host_out + off, src + off, (size_t)(r1 - r0) * f->width * px_bytes,
                                       hipMemcpyDeviceToHost, c->copy_stream));
         }
-        timed = false;  // ev1 already recorded after the last kernel
+    } else if (host_out) {
+        HIP_TRY(c, hipMemcpyAsync(host_out, src, (size_t)rows * f->width * px_bytes, hipMemcpyDeviceToHost, st));
     }
     if (timed) HIP_TRY(c, hipEventRecord(c->ev1, st));
     if (capturing) {
         c->captured = true;
-        if (cbuf) c->cb.pinned = true;
+        if (P.cbuf) c->cb.pinned = true;
     } else if (!sync_path) {  // (uploads and rt_destroy sync every such stream)
         note_async(c, st);
     }
@@ -3246,12 +3166,7 @@ static int finish_sync(rt_ctx* c, const rt_frame* f, hipStream_t st, bool timed)
     HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
     // c->stream waited for every async render enqueued before this call
     // (fence_async), so none is in flight any more
-    c->async_streams.clear();
-    c->state_pending = false;
-    c->state_stream = nullptr;
-    c->wf.pending = false;
-    c->ss.pending = false;
-    free_deferred(c);
+    settled(c);
     if (timed) {
         float ms = 0.f;
         HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
@@ -3306,27 +3221,65 @@ static int ensure_scratch(rt_ctx* c, size_t bytes)
     return RT_OK;
 }
 
+// The start of every synchronous call on c->stream: each state write and
+// render of the call comes after the async renders already enqueued on other
+// streams.
+static int sync_begin(rt_ctx* c)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = fence_async(c, c->stream)) return rc;
+    return wait_state(c, c->stream);
+}
+
+// The output planes (at most 3) of a synchronous render: a device pointer is
+// written in place, a host pointer through its part of the context's scratch
+// and copied back after the launch.
+struct SyncOut {
+    void *user[3] = {}, *target[3] = {};
+    bool host[3] = {};
+    size_t off[3] = {}, need = 0;
+    int n = 0;
+    // plane p (may be null: not requested), `reserve` bytes of scratch if it is a host plane
+    int add(void* p, size_t reserve)
+    {
+        user[n] = p;
+        host[n] = p && !is_device_ptr(p);
+        if (host[n]) {
+            off[n] = need;
+            need += reserve;
+        }
+        return n++;
+    }
+    // the device pointers to launch into
+    int place(rt_ctx* c)
+    {
+        if (need)
+            if (int rc = ensure_scratch(c, need)) return rc;
+        for (int i = 0; i < n; ++i) target[i] = host[i] ? (void*)((char*)c->d_scratch + off[i]) : user[i];
+        return RT_OK;
+    }
+    // after the launch: the bytes written to host plane i, to the caller
+    int copy_back(rt_ctx* c, int i, size_t bytes) const
+    {
+        if (host[i] && bytes) HIP_TRY(c, hipMemcpyAsync(user[i], target[i], bytes, hipMemcpyDeviceToHost, c->stream));
+        return RT_OK;
+    }
+};
+
 static int render_sync(rt_ctx* c, const rt_frame* f, void* out, bool as_float)
 {
     if (!c || !f || !out) return RT_E_ARG;
     if (c->cpu) return not_cpu(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    // every state write and render of this call comes after the async
-    // renders already enqueued on other streams
-    if (int rc = fence_async(c, c->stream)) return rc;
-    if (int rc = wait_state(c, c->stream)) return rc;
+    if (int rc = sync_begin(c)) return rc;
     const size_t px = (size_t)f->width * (size_t)std::max(0, frame_rows(f));
     const size_t bytes = px * (as_float ? 12 : 4);
-    const bool dev = is_device_ptr(out);
-    void* target = out;
-    if (!dev) {
-        int rc = ensure_scratch(c, std::max<size_t>(bytes, 16));
-        if (rc) return rc;
-        target = c->d_scratch;
-    }
-    int rc = launch(c, f, as_float ? nullptr : (unsigned*)target, as_float ? (float*)target : nullptr, c->stream, true,
-                    true, (!dev && bytes) ? out : nullptr);
-    if (rc) return rc;
+    SyncOut o;
+    o.add(out, std::max<size_t>(bytes, 16));
+    if (int rc = o.place(c)) return rc;
+    // (launch copies: a big slab goes to the host in chunks)
+    if (int rc = launch(c, f, as_float ? nullptr : (unsigned*)o.target[0], as_float ? (float*)o.target[0] : nullptr,
+                        c->stream, true, true, (o.host[0] && bytes) ? out : nullptr))
+        return rc;
     return finish_sync(c, f, c->stream, true);
 }
 
@@ -3347,15 +3300,11 @@ RT_EXPORT int rt_render_sequence_async(rt_ctx* c, const rt_frame* frames, int32_
 {
     if (!c || (n > 0 && !frames) || n < 0) return RT_E_ARG;
     if (c->cpu) return not_cpu(c);
-    if (!c->uploaded) {
-        c->err = "render before rt_upload_scene";
-        return RT_E_STATE;
-    }
+    if (int rc = check_uploaded(c)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(c, hipStreamIsCapturing(st, &cs));
-    const bool capturing = cs != hipStreamCaptureStatusNone;
+    bool capturing = false;
+    if (int rc = stream_capturing(c, st, &capturing)) return rc;
     // everything is checked before anything is enqueued
     for (int i = 0; i < n; ++i) {
         const rt_frame* f = frames + i;
@@ -3456,45 +3405,23 @@ RT_EXPORT int rt_prepare_camera(rt_ctx* c, const rt_frame* f)
 {
     if (!c || !f) return RT_E_ARG;
     if (c->cpu) return not_cpu(c);
-    if (!c->uploaded) {
-        c->err = "rt_prepare_camera before rt_upload_scene";
-        return RT_E_STATE;
-    }
-    if (!frame_ok(f)) {
-        c->err = "bad rt_frame geometry";
-        return RT_E_ARG;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = fence_async(c, c->stream)) return rc;
-    if (int rc = wait_state(c, c->stream)) return rc;
+    if (int rc = check_uploaded(c, "rt_prepare_camera")) return rc;
+    if (int rc = check_frame(c, f)) return rc;
+    if (int rc = sync_begin(c)) return rc;
     const int depth = reachable_depth(c, f);
     const bool cb_want = cam_lists(c, depth, lbuf_on(c)) && c->n_tri > 0 && c->opt_camera_buffer && cb_frame_ok(f);
     if (int rc = prepare_state(c, f, c->stream, true, false, cb_want)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->async_streams.clear();
-    c->state_pending = false;
-    c->state_stream = nullptr;
-    c->wf.pending = false;
-    c->ss.pending = false;
-    free_deferred(c);
+    settled(c);
     return RT_OK;
 }
 
 static int cpu_render_sync(rt_ctx* c, const rt_frame* f, uint8_t* rgba, float* rgb)
 {
     if (!c || !f || (!rgba && !rgb)) return RT_E_ARG;
-    if (!c->cpu) {
-        c->err = "rt_cpu_render needs a CPU context (rt_create_cpu)";
-        return RT_E_STATE;
-    }
-    if (!c->uploaded) {
-        c->err = "render before rt_upload_scene";
-        return RT_E_STATE;
-    }
-    if (!frame_ok(f)) {
-        c->err = "bad rt_frame geometry";
-        return RT_E_ARG;
-    }
+    if (!c->cpu) return needs_cpu(c, "rt_cpu_render");
+    if (int rc = check_uploaded(c)) return rc;
+    if (int rc = check_frame(c, f)) return rc;
     c->last = rt_stats{};
     double ms = 0.0;
     const int rc = cpu_render(c->cpu_scene, c->cpu_threads, f, frame_rows(f), rgba, rgb, &ms);
@@ -3529,23 +3456,18 @@ static int render_ss_sync(rt_ctx* c, const rt_frame* f, int s, void* out, bool a
     if (c->cpu) return not_cpu(c);
     if (int rc = ss_check(c, f, s)) return rc;
     if (s == 1) return render_sync(c, f, out, as_float);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = fence_async(c, c->stream)) return rc;
-    if (int rc = wait_state(c, c->stream)) return rc;
+    if (int rc = sync_begin(c)) return rc;
     const size_t px = (size_t)(f->width / s) * (size_t)ss_rows_of(f, s);
     const size_t bytes = px * (as_float ? 12 : 4);
-    const bool dev = is_device_ptr(out);
-    void* target = out;
-    if (!dev) {
-        if (int rc = ensure_scratch(c, std::max<size_t>(bytes, 16))) return rc;
-        target = c->d_scratch;
-    }
-    if (int rc = launch(c, f, as_float ? nullptr : (unsigned*)target, as_float ? (float*)target : nullptr, c->stream,
-                        true, true, nullptr, s))
+    SyncOut o;
+    o.add(out, std::max<size_t>(bytes, 16));
+    if (int rc = o.place(c)) return rc;
+    if (int rc = launch(c, f, as_float ? nullptr : (unsigned*)o.target[0], as_float ? (float*)o.target[0] : nullptr,
+                        c->stream, true, true, nullptr, s))
         return rc;
     // (a band set's rows past the frame are not written: they are not copied either)
     const size_t wrote = (size_t)(f->width / s) * (size_t)(ss_valid_rows(f, frame_rows(f)) / s) * (as_float ? 12 : 4);
-    if (!dev && wrote) HIP_TRY(c, hipMemcpyAsync(out, target, wrote, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = o.copy_back(c, 0, wrote)) return rc;
     return finish_sync(c, f, c->stream, true);
 }
 
@@ -3572,16 +3494,10 @@ RT_EXPORT int rt_render_ss_async(rt_ctx* c, const rt_frame* f, int32_t s, uint8_
 static int cpu_render_ss_sync(rt_ctx* c, const rt_frame* f, int s, uint8_t* rgba, float* rgb)
 {
     if (!c || !f || (!rgba && !rgb)) return RT_E_ARG;
-    if (!c->cpu) {
-        c->err = "rt_cpu_render_ss needs a CPU context (rt_create_cpu)";
-        return RT_E_STATE;
-    }
+    if (!c->cpu) return needs_cpu(c, "rt_cpu_render_ss");
     if (int rc = ss_check(c, f, s)) return rc;
     if (s == 1) return cpu_render_sync(c, f, rgba, rgb);
-    if (!c->uploaded) {
-        c->err = "render before rt_upload_scene";
-        return RT_E_STATE;
-    }
+    if (int rc = check_uploaded(c)) return rc;
     c->last = rt_stats{};
     const int rows = frame_rows(f);
     std::vector<float> samples((size_t)rows * f->width * 3);
@@ -3618,10 +3534,7 @@ static aov_fn aov_kernel(int wave)
 // The checks every AOV entry point shares (after the backend's own).
 static int aov_check(rt_ctx* c, const rt_frame* f, const rt_aov* o)
 {
-    if (!c->uploaded) {
-        c->err = "render before rt_upload_scene";
-        return RT_E_STATE;
-    }
+    if (int rc = check_uploaded(c)) return rc;
     if (!o->t && !o->id && !o->n) {
         c->err = "rt_render_aov: no output plane requested";
         return RT_E_ARG;
@@ -3630,11 +3543,7 @@ static int aov_check(rt_ctx* c, const rt_frame* f, const rt_aov* o)
         c->err = "rt_render_aov: RT_FLAG_STATS is not accepted";
         return RT_E_ARG;
     }
-    if (!frame_ok(f)) {
-        c->err = "bad rt_frame geometry";
-        return RT_E_ARG;
-    }
-    return RT_OK;
+    return check_frame(c, f);
 }
 
 // One AOV frame into device planes on st.  The variant: WAVE 0 (no camera
@@ -3648,11 +3557,8 @@ static int aov_check(rt_ctx* c, const rt_frame* f, const rt_aov* o)
 static int launch_aov(rt_ctx* c, const rt_frame* f, const rt_aov& dev, hipStream_t st, bool sync_path)
 {
     bool capturing = false;
-    if (!sync_path) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIP_TRY(c, hipStreamIsCapturing(st, &cs));
-        capturing = cs != hipStreamCaptureStatusNone;
-    }
+    if (!sync_path)
+        if (int rc = stream_capturing(c, st, &capturing)) return rc;
     const bool wave0 = c->n_tri == 0 || tiny_ok(c, 0, lbuf_on(c));
     const bool cb_want = !wave0 && c->opt_camera_buffer && cb_frame_ok(f);
     const int rows = frame_rows(f);
@@ -3692,35 +3598,20 @@ RT_EXPORT int rt_render_aov(rt_ctx* c, const rt_frame* f, const rt_aov* out)
     if (!c || !f || !out) return RT_E_ARG;
     if (c->cpu) return not_cpu(c);
     if (int rc = aov_check(c, f, out)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = fence_async(c, c->stream)) return rc;
-    if (int rc = wait_state(c, c->stream)) return rc;
-    // per plane: a device pointer is written in place, a host pointer through
-    // the context's scratch (one 256-byte aligned part per host plane)
+    if (int rc = sync_begin(c)) return rc;
+    // (one 256-byte aligned part of the scratch per host plane)
     const int rows = std::max(0, frame_rows(f));
     const size_t px = (size_t)f->width * (size_t)rows;
     void* const user[3] = {out->t, out->id, out->n};
-    const size_t bytes[3] = {px * 4, px * 4, px * 12};
-    bool host[3] = {false, false, false};
-    size_t off[3] = {0, 0, 0}, need = 0;
-    for (int i = 0; i < 3; ++i) {
-        host[i] = user[i] && !is_device_ptr(user[i]);
-        if (host[i]) {
-            off[i] = need;
-            need += (bytes[i] + 255) / 256 * 256;
-        }
-    }
-    if (need)
-        if (int rc = ensure_scratch(c, need)) return rc;
-    void* target[3];
-    for (int i = 0; i < 3; ++i) target[i] = host[i] ? (void*)((char*)c->d_scratch + off[i]) : user[i];
-    const rt_aov dev{(float*)target[0], (int32_t*)target[1], (float*)target[2]};
+    SyncOut o;
+    for (int i = 0; i < 3; ++i) o.add(user[i], (px * (i == 2 ? 12 : 4) + 255) / 256 * 256);
+    if (int rc = o.place(c)) return rc;
+    const rt_aov dev{(float*)o.target[0], (int32_t*)o.target[1], (float*)o.target[2]};
     if (int rc = launch_aov(c, f, dev, c->stream, true)) return rc;
     // (a band set's rows past the frame are not written: they are not copied either)
     const size_t wrote = (size_t)f->width * (size_t)ss_valid_rows(f, rows);
     for (int i = 0; i < 3; ++i)
-        if (host[i] && wrote)
-            HIP_TRY(c, hipMemcpyAsync(user[i], target[i], wrote * (i == 2 ? 12 : 4), hipMemcpyDeviceToHost, c->stream));
+        if (int rc = o.copy_back(c, i, wrote * (i == 2 ? 12 : 4))) return rc;
     return finish_sync(c, f, c->stream, rows > 0);
 }
 
@@ -3736,10 +3627,7 @@ RT_EXPORT int rt_render_aov_async(rt_ctx* c, const rt_frame* f, const rt_aov* de
 RT_EXPORT int rt_cpu_render_aov(rt_ctx* c, const rt_frame* f, const rt_aov* out)
 {
     if (!c || !f || !out) return RT_E_ARG;
-    if (!c->cpu) {
-        c->err = "rt_cpu_render_aov needs a CPU context (rt_create_cpu)";
-        return RT_E_STATE;
-    }
+    if (!c->cpu) return needs_cpu(c, "rt_cpu_render_aov");
     if (int rc = aov_check(c, f, out)) return rc;
     c->last = rt_stats{};
     const int rows = frame_rows(f);
@@ -3892,6 +3780,20 @@ RT_EXPORT int rt_debug_lb_region_build(const unsigned* off, int R, double* out5)
     out5[4] = lb_region_build(off, R, rg);
     for (int q = 0; q < 4; ++q) out5[q] = rg[q];
     return RT_OK;
+}
+
+// The row chunks of a frame, no device (rt_debug.h, rt_chunks.h).
+RT_EXPORT int rt_debug_row_chunks(int width, int rows, int band_rows, int px_bytes, int ss, int wf, int host_out,
+                                  double host_chunk_mb, double ss_chunk_rows, int* bounds, int cap)
+{
+    if (!bounds || width <= 0 || rows <= 0 || px_bytes <= 0 || ss < 1) return RT_E_ARG;
+    const int step = row_chunk_step(width, rows, band_rows, px_bytes, ss, wf != 0, host_out != 0, host_chunk_mb,
+                                    ss_chunk_rows);
+    if (step <= 0) return RT_E_ARG;
+    const int n = (rows + step - 1) / step;
+    if (cap < n + 1) return RT_E_ARG;
+    for (int i = 0; i <= n; ++i) bounds[i] = std::min(rows, i * step);
+    return n;
 }
 
 // Diagnostic (include/rt_debug.h): camera-buffer summary: out[0] = current

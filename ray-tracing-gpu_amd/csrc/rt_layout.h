@@ -256,6 +256,69 @@ __device__ int rt_prof_ntiles;
     } while (0)
 #endif
 
+// All 64 lanes of the wave are active (rt_cull.h: the wave-level tests).
+__device__ __forceinline__ bool wave_full() { return __builtin_amdgcn_read_exec() == ~0ull; }
+// Sum over all 64 lanes (full exec only), for the stats tallies.
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+    // the stats launch is untimed: 64 scalar reads are simple and exact
+    unsigned long long t = 0;
+    for (int l = 0; l < 64; ++l) {
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+        t += ((unsigned long long)hi << 32) | lo;
+    }
+    return t;
+}
+
+// ---- the end of a tile (trace_tile, rt_trace_tiny)
+// RT_PROF builds: lane 0 adds the wave's section clocks and event counts to
+// the totals and writes the tile's record.
+__device__ __forceinline__ void tile_prof_flush(Counters& cnt)
+{
+#ifdef RT_PROF
+    RT_MARK(cnt, 6);
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long tot = 0;
+        for (int i = 0; i < 8; ++i) {
+            atomicAdd(&rt_prof_acc[i], cnt.pt[i]);
+            atomicAdd(&rt_prof_ev[i], (unsigned long long)cnt.ev[i]);
+            tot += cnt.pt[i];
+        }
+        const int tile = (int)(blockIdx.y * gridDim.x + blockIdx.x);
+        if (rt_prof_tiles && tile < rt_prof_ntiles) {
+            unsigned* o = rt_prof_tiles + 16 * (size_t)tile;
+            o[0] = (unsigned)tot;
+            o[1] = (unsigned)(tot >> 32);
+            for (int i = 0; i < 8; ++i) o[2 + i] = (unsigned)(cnt.pt[i] >> 8);
+            const int evi[6] = {1, 2, 4, 5, 6, 7};  // cam member batches, cam exact, shadow member
+            for (int i = 0; i < 6; ++i) o[10 + i] = cnt.ev[evi[i]];  // batches, exact, by dcap, by cone
+        }
+    }
+#endif
+}
+// The RT_FLAG_STATS launch's tallies into the block's stats slot; all_lanes:
+// every lane of the wave is known to run (else wave_full() decides): then one
+// atomic per counter per wave.
+__device__ __forceinline__ void tile_tally(const Counters& cnt, StatsDev* stats, bool all_lanes)
+{
+    unsigned long long v[9] = {cnt.primary, cnt.bounce, cnt.shadow, cnt.skipped, cnt.tri,
+                               cnt.pla,     cnt.qua,    cnt.btri,   cnt.bnode};
+    StatsDev* sl = stats + ((blockIdx.x + blockIdx.y * gridDim.x) % kStatSlots);
+    unsigned long long* dst[9] = {&sl->primary, &sl->bounce, &sl->shadow, &sl->skipped, &sl->tri,
+                                  &sl->pla,     &sl->qua,    &sl->btri,   &sl->bnode};
+    if (all_lanes || wave_full()) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const unsigned long long w = wave_sum_u64(v[i]);
+            if ((threadIdx.x & 63) == 0) atomicAdd(dst[i], w);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) atomicAdd(dst[i], v[i]);
+    }
+}
+
 // ----------------------------------------------------- exact fast reciprocal
 // IEEE 1.0f/x in 3 VALU instead of the ~10-instruction division expansion:
 // rcp_nr (rt_fastmath.h: v_rcp_f32 then one FMA Newton step), checked by

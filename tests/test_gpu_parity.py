@@ -388,6 +388,30 @@ def test_launch_camera_equals_device_camera_state(i, w, h):
         a.set_option("host_chunk_mb", 8)
 
 
+@pytest.mark.parametrize("i,depth,opts", [(2, 0, dict(launch_camera=0)), (7, 3, {})],
+                         ids=["wave-culling-camera-buffer", "bounce"])
+def test_host_chunked_output_equals_whole(i, depth, opts):
+    """Host output in row chunks (each chunk a launch of its own, its copy on
+    the copy stream) against the same context's whole-frame render, bit for
+    bit: 64 x 100 float in seven chunks, the last of 4 rows (RGBA8: two), for
+    the wave-culling kernel with its camera buffer and for a bounce kernel."""
+    w, h = 64, 100
+    s = rt_amd.Scene(scene(i), w, h, depth)
+    c = rt_amd.Context(0, **opts)
+    c.upload(s)
+    whole8, wholef = c.render(s.frame), c.render_float(s.frame)
+    label = c.stats().kernel
+    assert label.startswith("rt_trace_kernel<") and label.startswith("rt_trace_kernel<0,") == (depth == 0), label
+    c.set_option("host_chunk_mb", w * h * 12 / 8 / 1048576.0 / 1.01)
+    try:
+        got8, gotf = c.render(s.frame), c.render_float(s.frame)
+        assert c.stats().kernel == label
+    finally:
+        c.set_option("host_chunk_mb", 8)
+    assert np.array_equal(got8, whole8)
+    assert bits_equal(gotf, wholef)
+
+
 def test_camera_buffer_after_bounce_frame(tmp_path):
     """A big scene rendered first with bounces (no camera buffer, so camera
     records only for <= 256 triangles), then at depth 0 from the same
