@@ -262,6 +262,7 @@ typedef struct {
     float intens;/* m_Intensite (default 0)                 */
 } olight;
 
+#define ORACLE_LEVELS 64   /* depths counted apart; deeper ones share the last slot */
 typedef struct oracle_scene {
     int w, h;
     int max_bounces;      /* Scene.cpp:68 m_NbRebondsMax            */
@@ -278,7 +279,15 @@ typedef struct oracle_scene {
     float half_w, half_h, inv_w, inv_h;
     int prepared;
     char err[256];
+    /* the last render's bounce tree by depth (oracle_level_counts) */
+    unsigned long long lvl_rays[ORACLE_LEVELS], lvl_parents[ORACLE_LEVELS];
 } oracle_scene;
+
+/* Per-thread tallies of the render in progress: rays traced at each depth
+ * (depth 0: the camera rays) and hits at each depth that spawned a child.
+ * oracle_render_window sums them into the scene; nothing reads them while
+ * a pixel is computed, so the rendered bits do not depend on them. */
+static __thread unsigned long long tl_rays[ORACLE_LEVELS], tl_parents[ORACLE_LEVELS];
 
 typedef struct {
     ov3 o, d;
@@ -696,8 +705,11 @@ static ocol shade(const oracle_scene* S, const oray* r, const ohit* h)
             }
         }
     }
+    int lvl = r->bounces < ORACLE_LEVELS ? r->bounces : ORACLE_LEVELS - 1;
     /* reflection (Scene.cpp:1779-1788, commented in the reference) */
     float er = s->kr * r->energy;
+    float et = s->kt * r->energy;
+    if ((er > S->min_energy || et > S->min_energy) && r->bounces < S->max_bounces) tl_parents[lvl]++;
     if (er > S->min_energy && r->bounces < S->max_bounces) {
         oray c;
         c.d = v3_reflect(r->d, h->n);
@@ -708,7 +720,6 @@ static ocol shade(const oracle_scene* S, const oray* r, const ohit* h)
         col_addeq(&res, col_scale(obtenir_couleur(S, &c), s->kr));
     }
     /* refraction (Scene.cpp:1790-1823, commented in the reference) */
-    float et = s->kt * r->energy;
     if (et > S->min_energy && r->bounces < S->max_bounces) {
         float ratio;
         oray c;
@@ -734,6 +745,7 @@ static ocol shade(const oracle_scene* S, const oray* r, const ohit* h)
 static ocol obtenir_couleur(const oracle_scene* S, const oray* r)
 {
     ohit best = {-1, -1.0f, {0, 0, 0}};
+    tl_rays[r->bounces < ORACLE_LEVELS ? r->bounces : ORACLE_LEVELS - 1]++;
     for (int i = 0; i < S->nsurf; i++) {
         ohit h = isect(S, i, r);
         if (h.t > O_EPS && (h.t < best.t || best.t < 0)) best = h;
@@ -842,20 +854,51 @@ OEXPORT int oracle_render_window(oracle_scene* S, int row0, int row1, int col0, 
     if (!S || !S->prepared) return -1;
     if (row0 < 0 || row1 > S->h || row0 > row1 || col0 < 0 || col1 > S->w || col0 > col1) return -2;
     int ww = col1 - col0;
+    memset(S->lvl_rays, 0, sizeof S->lvl_rays);
+    memset(S->lvl_parents, 0, sizeof S->lvl_parents);
 #ifdef _OPENMP
     if (nthreads < 1) nthreads = 1;
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
+#pragma omp parallel num_threads(nthreads)
 #endif
-    for (int y = row0; y < row1; y++) {
-        for (int x = col0; x < col1; x++) {
-            ocol c = pixel(S, x, y);
-            float* o = rgb + ((size_t)(y - row0) * ww + (x - col0)) * 3;
-            o[0] = c.r;
-            o[1] = c.g;
-            o[2] = c.b;
+    {
+        memset(tl_rays, 0, sizeof tl_rays);
+        memset(tl_parents, 0, sizeof tl_parents);
+#ifdef _OPENMP
+#pragma omp for schedule(dynamic, 1)
+#endif
+        for (int y = row0; y < row1; y++) {
+            for (int x = col0; x < col1; x++) {
+                ocol c = pixel(S, x, y);
+                float* o = rgb + ((size_t)(y - row0) * ww + (x - col0)) * 3;
+                o[0] = c.r;
+                o[1] = c.g;
+                o[2] = c.b;
+            }
+        }
+#ifdef _OPENMP
+#pragma omp critical(oracle_levels)
+#endif
+        for (int L = 0; L < ORACLE_LEVELS; L++) {
+            S->lvl_rays[L] += tl_rays[L];
+            S->lvl_parents[L] += tl_parents[L];
         }
     }
     (void)nthreads;
+    return 0;
+}
+
+/* The last oracle_render_window's (or oracle_render's) bounce tree by depth,
+ * n entries each: rays[L] = rays traced at depth L (rays[0]: the camera
+ * rays), parents[L] = depth-L hits that spawned at least one child under the
+ * gates of Scene.cpp:1780 and :1791 as shade() restates them.  Entries past
+ * ORACLE_LEVELS read 0. */
+OEXPORT int oracle_level_counts(oracle_scene* S, unsigned long long* rays, unsigned long long* parents, int n)
+{
+    if (!S || !rays || !parents || n < 0) return -1;
+    for (int L = 0; L < n; L++) {
+        rays[L] = L < ORACLE_LEVELS ? S->lvl_rays[L] : 0;
+        parents[L] = L < ORACLE_LEVELS ? S->lvl_parents[L] : 0;
+    }
     return 0;
 }
 

@@ -228,8 +228,13 @@ struct Ray {
 
 // Scene.cpp:1705-1826: colour of a ray, with the commented reflect / refract
 // block (:1779-1823) re-enabled below max_bounces as the GPU path does.
+// (tl_rays: this thread's rays of the render in progress, camera rays and
+// bounce rays — rt_stats' primary_rays / bounce_rays of an RT_FLAG_STATS frame)
+static thread_local unsigned long long tl_rays[2];
+
 static Color trace(const Scene& S, const rt_frame& f, const Ray& r)
 {
+    ++tl_rays[r.bounces > 0];
     const Hit h = closest(S, r.O, r.D);
     if (h.file < 0) return Color{f.background[0], f.background[1], f.background[2]};
     const Material& m = S.mat[h.file];
@@ -341,18 +346,25 @@ static int out_row(const rt_frame& f, int q)
     return (b * f.band_count + f.band_index) * f.band_rows + q % f.band_rows;
 }
 
-int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uint8_t* rgba, float* rgb, double* ms)
+int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uint8_t* rgba, float* rgb, double* ms,
+               unsigned long long* rays2)
 {
     using namespace cpu;
     const Scene& S = *static_cast<const Scene*>(handle);
     const auto t0 = std::chrono::steady_clock::now();
     const int W = f->width;
     std::atomic<int> next{0};
+    std::atomic<unsigned long long> primary{0}, bounce{0};
     constexpr int kBand = 8;
     auto work = [&]() {
+        tl_rays[0] = tl_rays[1] = 0;
         for (;;) {
             const int q0 = next.fetch_add(kBand);
-            if (q0 >= rows) return;
+            if (q0 >= rows) {
+                primary += tl_rays[0];
+                bounce += tl_rays[1];
+                return;
+            }
             for (int q = q0; q < std::min(rows, q0 + kBand); ++q) {
                 const int y = out_row(*f, q);
                 for (int x = 0; x < W; ++x) {
@@ -385,6 +397,10 @@ int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uin
     work();
     for (auto& t : pool) t.join();
     if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rays2) {
+        rays2[0] = primary;
+        rays2[1] = bounce;
+    }
     return RT_OK;
 }
 

@@ -10,8 +10,10 @@ namespace rt {
 int cpu_upload(void** handle, const rt_scene_flat* s);
 void cpu_free(void* handle);
 // Render `rows` output rows of frame f (slab or band set) on `threads` host
-// threads (<= 0: all); either output may be null.  *ms = wall time.
-int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uint8_t* rgba8, float* rgb, double* ms);
+// threads (<= 0: all); either output may be null.  *ms = wall time; rays2
+// (may be null) = the camera rays and the bounce rays traced.
+int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uint8_t* rgba8, float* rgb, double* ms,
+               unsigned long long* rays2 = nullptr);
 // The primary-hit AOV planes of the same rows (rt.h rt_render_aov: t, file
 // index, normal; a miss is -1, -1, 0); each output may be null.
 int cpu_render_aov(const void* handle, int threads, const rt_frame* f, int rows, float* t, int32_t* id, float* n,

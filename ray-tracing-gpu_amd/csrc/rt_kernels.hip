@@ -3424,8 +3424,13 @@ static int cpu_render_sync(rt_ctx* c, const rt_frame* f, uint8_t* rgba, float* r
     if (int rc = check_frame(c, f)) return rc;
     c->last = rt_stats{};
     double ms = 0.0;
-    const int rc = cpu_render(c->cpu_scene, c->cpu_threads, f, frame_rows(f), rgba, rgb, &ms);
+    unsigned long long rays2[2] = {0, 0};
+    const int rc = cpu_render(c->cpu_scene, c->cpu_threads, f, frame_rows(f), rgba, rgb, &ms, rays2);
     c->last.kernel_ms = (float)ms;
+    if (f->flags & RT_FLAG_STATS) {  // (the rays only: the CPU backend counts no tests)
+        c->last.primary_rays = rays2[0];
+        c->last.bounce_rays = rays2[1];
+    }
     return rc;
 }
 

@@ -436,19 +436,34 @@ def test_wavefront_sort_orders_render_the_same(hfr, hfr_golden, sort):
         ctx.set_option("wf_sort", 1)
 
 
+def _wf_stragglers(ctx):
+    """The last wavefront frame's straggling walks per level 0 .. 8."""
+    L = rt_amd.lib()
+    L.rt_debug_wf_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    out = (ctypes.c_uint * 27)()
+    assert L.rt_debug_wf_counts(ctx._h, out, 27) == 0, ctx._err()
+    return list(out)[2::3]
+
+
 def test_straggler_overlap_renders_the_same(hfr, hfr_golden):
     """RT_OPT_WF_OVERLAP (the stragglers' walks and shading on a second
     stream beside each level's shade launch) on and off: the same images, and
-    the reference's windows at d3 and d6 with it off."""
+    the reference's windows at d3 and d6 with it off.  Both ways some walks
+    must go over the trace launch's budget (rt_debug_wf_counts' third word per
+    level), or the straggler path — kWfPending, hit2, rt_wf_straggle, the
+    shade launch's STRAG variant — is not what the images compare."""
     ctx, get = hfr
     for d in (3, 6):
         f = get(1920, 1080, d).frame
         on = ctx.render_float(f)
+        strag_on = _wf_stragglers(ctx)
         ctx.set_option("wf_overlap", 0)
         try:
             off = ctx.render_float(f)
+            strag_off = _wf_stragglers(ctx)
         finally:
             ctx.set_option("wf_overlap", 1)
+        assert max(strag_on[1:d + 1]) > 0 and max(strag_off[1:d + 1]) > 0, (d, strag_on, strag_off)
         assert bits_equal(on, off), d
         for win, want, k in _groups(hfr_golden)[(1920, 1080, d)]:
             r0, r1, c0, c1 = win

@@ -22,6 +22,12 @@ def ctx():
     return rt_amd.Context(0)
 
 
+# the big scenes rendered with bounces (depth = seed % 6 >= 1): seed -> the
+# kernel label of its frame in test_fuzz_scene_matches_oracle
+BIG_BOUNCE_SEEDS = (17, 37, 57, 77, 97, 117)
+KERNELS = {}
+
+
 @pytest.mark.parametrize("seed", range(120))
 def test_fuzz_scene_matches_oracle(ctx, oracle, tmp_path, seed):
     specular = seed % 3 == 2
@@ -34,11 +40,34 @@ def test_fuzz_scene_matches_oracle(ctx, oracle, tmp_path, seed):
     want = oracle.render(str(path), w, h, depth)
     ctx.upload(s)
     got = ctx.render_float(s.frame)
+    if seed in BIG_BOUNCE_SEEDS:
+        KERNELS[seed] = ctx.stats().kernel
     if specular:
         assert ulp_diff(got, want) <= 8
         assert np.abs(rgba8(got).astype(int) - rgba8(want).astype(int)).max() <= 1
     else:
         assert bits_equal(got, want), f"max |d| {np.abs(got - want).max()} ulps {ulp_diff(got, want)}"
+
+
+def test_big_fuzz_scenes_render_as_wavefronts(ctx, tmp_path):
+    """The six big scenes with bounces are the fuzz test's wavefront frames:
+    at least three of them must still take that path (a change of the
+    kernel selection that moved them all to the megakernel would leave the
+    images right and the wavefront levels unfuzzed).  Today seeds 37, 57, 77
+    and 97 do (1, 3, 5 and 1 levels); 17 and 117 have no light, so no light
+    buffer and no BVH kernels.  Seeds whose frame the test above did not
+    render in this run are rendered here."""
+    for seed in BIG_BOUNCE_SEEDS:
+        if seed not in KERNELS:
+            path = tmp_path / f"fuzz{seed}.dat"
+            path.write_text(fuzz_dat(seed, seed % 3 == 2, True))
+            s = rt_amd.Scene(str(path), 64, 48, seed % 6)
+            ctx.upload(s)
+            ctx.render_float(s.frame)
+            KERNELS[seed] = ctx.stats().kernel
+    wavefronts = sorted(seed for seed in BIG_BOUNCE_SEEDS if KERNELS[seed].startswith("wavefront"))
+    print("wavefront seeds:", wavefronts, {k: KERNELS[k] for k in BIG_BOUNCE_SEEDS})
+    assert len(wavefronts) >= 3, KERNELS
 
 
 def _assemble(ctx, s, h, n, band_rows):
