@@ -46,6 +46,7 @@
 #define RT_AMD_RT_BVH_H
 
 #include "rt_cull.h"
+#include "rt_dims.h"
 
 #pragma clang fp contract(off)
 
@@ -56,8 +57,7 @@ namespace rt {
 // entries, 0 in the wavefront's trace kernel): entry i of lane l at word
 // 64 i + l (lane-contiguous rows, no bank conflicts).  A path of d inner
 // nodes pushes at most d entries: the launch gives depth x 256 bytes, and
-// the host enables the BVH only for depth <= kBvhStack.
-constexpr int kBvhStack = 24;
+// the host enables the BVH only for depth <= kBvhStack (rt_dims.h).
 constexpr size_t kBvhLdsBytes = (size_t)kBvhStack * 64 * sizeof(int);
 
 template <size_t WIN>

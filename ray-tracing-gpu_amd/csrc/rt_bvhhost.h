@@ -1,5 +1,6 @@
-// rt_bvhhost.h — host build of the bounce-ray BVH (rt_bvh.h), at upload.
-// Part of the host half of rt_kernels.hip (included after rt_ctx).
+// rt_bvhhost.h — host build of the bounce-ray BVH (rt_bvh.h), at upload
+// (rt_scenehost.h scene_host_build).  Plain host C++: the library compiles it
+// with HIP's float4, a stand-alone host program with the one below.
 //
 // A binned-SAH BVH2 over every triangle of tri[] (opaque and translucent:
 // closest hit does not care), leaves of at most 4 triangles, inner nodes
@@ -14,6 +15,15 @@
 #include <cmath>
 #include <cstring>
 #include <vector>
+
+#include "rt_dims.h"
+
+#if !defined(__HIPCC__) && !defined(__HIP__)
+struct float4 {
+    float x, y, z, w;
+};
+inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+#endif
 
 namespace rt {
 

@@ -35,7 +35,6 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/rt.h"
@@ -47,6 +46,7 @@
 #include "rt_bvh.h"
 #include "rt_wavefront.h"
 #include "rt_resolve.h"
+#include "rt_scenehost.h"  // scene_host_build, lb_plan; kClusterMinTriangles, RT_BVH_MIN_TRIANGLES
 
 #pragma clang fp contract(off)
 
@@ -711,7 +711,7 @@ using namespace rt;
 constexpr int kSeqSlots = RT_SEQ_STREAMS;
 constexpr int kCbWordSets = 16;  // camera buffers per context: 1 + sequence slots (spare sets)
 
-struct rt_ctx {
+struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
     int device = 0;
     // CPU backend (rt_create_cpu): no HIP object is ever made for it
     bool cpu = false;
@@ -872,11 +872,6 @@ struct rt_ctx {
     std::vector<double> far_ladder;       // big lists' far light buffers
     double upload_parts_ms[4] = {0, 0, 0, 0};  // copy+records, prepasses, light buffer, total
     double lb_parts_ms[5] = {0, 0, 0, 0, 0};    // lb_build phases (rt_debug_upload_info out[4..8])
-    int n_surf = 0, n_lights = 0;
-    int n_tri = 0, n_plane = 0, n_quad = 0;
-    int n_tri_opaque = 0, n_plane_opaque = 0, n_quad_opaque = 0, n_translucent = 0;
-    int shadow_split = 0;
-    float k_max = 0.0f;         // max(Kr, Kt) over surfaces (NaN ignored)
     // bounce-ray BVH (rt_bvh.h, built at upload for scenes that can bounce)
     float4* d_bvh_node = nullptr;
     float4* d_bvh_tri = nullptr;
@@ -928,7 +923,6 @@ struct rt_ctx {
     int opt_xcd_stripe = 0;     // RT_OPT_XCD_STRIPE
     bool opt_lb_unroll = true;  // RT_OPT_LB_UNROLL
     bool opt_lb_region = true;  // RT_OPT_LB_REGION
-    float kr_max = 0.0f, kt_max = 0.0f;  // max Kr, max Kt over surfaces
     bool uploaded = false;
     rt_stats last{};
     std::string err;
@@ -1201,6 +1195,53 @@ static int not_cpu(rt_ctx* c)
     return RT_E_STATE;
 }
 
+template <class... P>
+static void free_all(P*&... p)
+{
+    ((hipFree(p), p = nullptr), ...);
+}
+
+// The light buffer: dropped with the scene, and by a build that turns out
+// too large (lb_build: the scene then runs without it).
+static void lb_drop(rt_ctx* c)
+{
+    free_all(c->d_lb_off, c->d_lb_ent, c->d_lb_dcap, c->d_lb_meta);
+    c->h_lb_meta.clear();
+    c->lb_ready = false;
+    c->lb_levels = c->lb_r0 = 0;
+    c->lb_entries = 0;
+}
+
+// Everything an upload makes: the scene's device buffers, the host copies and
+// the per-scene counts and flags.  The one place that lists them: an upload
+// drops the previous scene with it (a failed one leaves its pieces for the
+// next), rt_destroy the last.  Nothing may be in flight (sync_all).  The
+// camera buffers stay (reallocated on demand): they are only marked stale.
+static void scene_drop(rt_ctx* c)
+{
+    c->uploaded = false;
+    free_all(c->d_geom, c->d_mat, c->d_lights, c->d_tri, c->d_plane, c->d_quad, c->d_translucent, c->d_tricam,
+             c->d_trisph, c->d_cone_cam, c->d_cone_light, c->d_trinrm, c->d_tricoef, c->d_clu_cam, c->d_clu_light,
+             c->d_uni, c->d_lrec, c->d_bvh_node, c->d_bvh_tri, c->d_skey);
+    lb_drop(c);
+    c->lb_build_ms = 0.0;
+    for (auto& q : c->seq) {  // the sequence slots' per-camera records
+        free_all(q.tricam, q.cone_cam, q.clu_cam, q.uni);
+        q.cb.valid = false;
+    }
+    for (auto* h : {&c->h_lrec, &c->h_tri, &c->h_sph, &c->h_nrm, &c->h_coef}) h->clear();
+    c->h_plane.clear();
+    c->n_clu = 0;
+    c->nbin_half = 0;
+    c->bvh_inner = c->bvh_leaves = c->bvh_depth = 0;
+    c->bvh_build_ms = 0.0;
+    c->cb.valid = false;
+    c->cam_valid = false;
+    c->tiny_valid = false;
+    for (auto& q : c->tiny_masks) q.valid = q.pend_valid = false;  // the old scene's triangles
+    static_cast<SceneCounts&>(*c) = SceneCounts{};
+}
+
 RT_EXPORT void rt_destroy(rt_ctx* c)
 {
     if (!c) return;
@@ -1214,36 +1255,13 @@ RT_EXPORT void rt_destroy(rt_ctx* c)
         (void)sync_all(c);
     }
     free_retired(c);
-    hipFree(c->d_geom);
-    hipFree(c->d_mat);
-    hipFree(c->d_lights);
-    hipFree(c->d_tri);
-    hipFree(c->d_plane);
-    hipFree(c->d_quad);
-    hipFree(c->d_translucent);
-    hipFree(c->d_tricam);
-    hipFree(c->d_trisph);
-    hipFree(c->d_cone_cam);
-    hipFree(c->d_cone_light);
-    hipFree(c->d_trinrm);
-    hipFree(c->d_tricoef);
-    hipFree(c->d_clu_cam);
-    hipFree(c->d_clu_light);
-    hipFree(c->d_lb_off);
-    hipFree(c->d_lb_ent);
-    hipFree(c->d_lb_dcap);
-    hipFree(c->d_lb_meta);
-    hipFree(c->d_lrec);
-    hipFree(c->d_uni);
-    hipFree(c->d_bvh_node);
-    hipFree(c->d_bvh_tri);
+    scene_drop(c);
     hipFree(c->wf.mem);
     hipFree(c->wf.kin);
     hipFree(c->wf.kout);
     hipFree(c->wf.kout2);
     hipFree(c->wf.hist);
     hipFree(c->wf.bsum);
-    hipFree(c->d_skey);
     hipFree(c->ss.mem);
     if (c->ss.ev) hipEventDestroy(c->ss.ev);
     if (c->wf.ev) hipEventDestroy(c->wf.ev);
@@ -1255,13 +1273,7 @@ RT_EXPORT void rt_destroy(rt_ctx* c)
         if (q.ev) hipEventDestroy(q.ev);
     }
     cb_free(c->cb);
-    for (auto& q : c->seq) {
-        hipFree(q.tricam);
-        hipFree(q.cone_cam);
-        hipFree(q.clu_cam);
-        hipFree(q.uni);
-        cb_free(q.cb);
-    }
+    for (auto& q : c->seq) cb_free(q.cb);
     hipFree(c->d_stats);
     hipFree(c->d_scratch);
     if (c->ev0) hipEventDestroy(c->ev0);
@@ -1283,14 +1295,6 @@ RT_EXPORT void rt_destroy(rt_ctx* c)
     delete c;
 }
 
-static bool nonneg_finite(float v) { return std::isfinite(v) && !std::signbit(v); }
-
-#include "rt_bvhhost.h"
-// Bounce rays walk the BVH (rt_bvh.h) in scenes of at least this many
-// triangles (fewer: every triangle, by wave-uniform scalar loads).
-#ifndef RT_BVH_MIN_TRIANGLES
-#define RT_BVH_MIN_TRIANGLES 64
-#endif
 
 // 256 camera records = 16 KB, the scalar data cache.
 static constexpr int kTricamMaxTriangles = 256;
@@ -1298,54 +1302,6 @@ static constexpr int kTricamMaxTriangles = 256;
 #define RT_EDGE_MAX_TRIANGLES 0x7fffffff  // every list size (SceneDev::use_edges)
 #endif
 static constexpr int kEdgeMaxTriangles = RT_EDGE_MAX_TRIANGLES;
-// two-level (clustered) culling above this many triangles
-static constexpr int kClusterMinTriangles = 1024;
-
-// Cluster order for the two-level culling: a top-down median split of the
-// centroids on the longest axis of their bounds, at multiples of 64, so
-// every run of 64 consecutive triangles is a compact leaf (a Morton order
-// scatters clusters of meshes with a thin, noisy axis: C3 cluster cones
-// 34 mrad median, 94 at the 90th percentile vs the members' 7.6).
-static void kd_order(std::vector<size_t>& ord, const std::vector<double>& cen, size_t b, size_t e)
-{
-    while (e - b > 64) {
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (size_t i = b; i < e; ++i)
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = std::min(lo[a], cen[3 * ord[i] + a]);
-                hi[a] = std::max(hi[a], cen[3 * ord[i] + a]);
-            }
-        int ax = 0;
-        for (int a = 1; a < 3; ++a)
-            if (hi[a] - lo[a] > hi[ax] - lo[ax]) ax = a;
-        const size_t n = e - b;
-        const size_t mid = b + std::max<size_t>(64, ((n / 2 + 32) / 64) * 64);
-        std::nth_element(ord.begin() + b, ord.begin() + mid, ord.begin() + e, [&](size_t x, size_t y) {
-            return cen[3 * x + ax] < cen[3 * y + ax] || (cen[3 * x + ax] == cen[3 * y + ax] && x < y);
-        });
-        kd_order(ord, cen, b, mid);
-        b = mid;
-    }
-}
-// Reorder 12-float triangle records into clusters, the ranges [0, n_opaque)
-// and [n_opaque, n) separately.
-static void cluster_order(std::vector<float>& tri, int n_opaque)
-{
-    const size_t n = tri.size() / 12;
-    std::vector<double> cen(3 * n);
-    for (size_t k = 0; k < n; ++k)
-        for (int a = 0; a < 3; ++a) {
-            const double v = tri[12 * k + a] + (tri[12 * k + 3 + a] + (double)tri[12 * k + 6 + a]) / 3.0;
-            cen[3 * k + a] = std::isfinite(v) ? v : 0.0;
-        }
-    std::vector<size_t> ord(n);
-    for (size_t k = 0; k < n; ++k) ord[k] = k;
-    kd_order(ord, cen, 0, (size_t)n_opaque);
-    kd_order(ord, cen, (size_t)n_opaque, n);
-    std::vector<float> out(tri.size());
-    for (size_t k = 0; k < n; ++k) std::memcpy(&out[12 * k], &tri[12 * ord[k]], 12 * sizeof(float));
-    tri.swap(out);
-}
 
 // Light buffer of every light (shadow_opaque_lb, lb_cone): resolution from
 // the median angular radius of the light's triangle cones (cell half-width
@@ -1375,21 +1331,74 @@ static void cluster_order(std::vector<float>& tri, int n_opaque)
 #endif
 // Slots: one buffer per entry of `cones` (a light's cone records, built for
 // the distance dcov[j]): the lights, then (big lists) their far buffers.
-#ifndef RT_LB_RMIN
-#define RT_LB_RMIN 128
-#endif
-static int lb_build(rt_ctx* c, int ntr, int n_opaque, const std::vector<const float4*>& cones,
-                    const std::vector<double>& dcov)
-{
-    hipStream_t st = c->stream;
-    const int nl = (int)cones.size();
-    const auto t0 = std::chrono::steady_clock::now();
-    auto tp = t0;
-    auto mark = [&](int i) {
+
+// Device temporaries of one build: freed when the scope ends, on every path
+// out of it.
+struct DevScope {
+    void* p[8] = {};
+    int n = 0;
+    DevScope() = default;
+    DevScope(const DevScope&) = delete;
+    ~DevScope()
+    {
+        for (int i = 0; i < n; ++i) hipFree(p[i]);
+    }
+    template <class T>
+    hipError_t alloc(T** out, size_t bytes)
+    {
+        assert(n < 8);
+        const hipError_t e = hipMalloc((void**)out, bytes);
+        if (e == hipSuccess) p[n++] = *out;
+        return e;
+    }
+};
+
+// lb_build's phases (rt_ctx::lb_parts_ms): mark(i) ends phase i.
+struct LbClock {
+    rt_ctx* c;
+    std::chrono::steady_clock::time_point tp = std::chrono::steady_clock::now();
+    void mark(int i)
+    {
         const auto now = std::chrono::steady_clock::now();
         c->lb_parts_ms[i] = std::chrono::duration<double, std::milli>(now - tp).count();
         tp = now;
-    };
+    }
+};
+
+constexpr int kLbTooLarge = 1;  // lb_level, lb_lists: no error, but the lists do not fit 32-bit indices
+
+// One level of lists for every slot: launch(j, false) adds slot j's counts
+// to off[] (`words` zeroed words), ONE scan turns them into offsets, the total
+// comes back (a host sync; it ends phase `part` if >= 0), alloc(total) makes
+// the lists and launch(j, true) fills them.  kLbTooLarge: total > max_total.
+template <class Launch, class Alloc>
+static int lb_level(rt_ctx* c, LbClock& clk, int part, int nl, unsigned* off, size_t words,
+                    unsigned long long max_total, unsigned long long* total, Launch launch, Alloc alloc)
+{
+    hipStream_t st = c->stream;
+    for (int j = 0; j < nl; ++j)
+        if (int rc = launch(j, false)) return rc;
+    unsigned long long* tot = nullptr;
+    HIP_TRY(c, scan_u32(off, (unsigned)words, off, (unsigned long long*)c->d_scan, st, &tot));
+    HIP_TRY(c, hipMemcpyAsync(c->h_word, tot, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    *total = *c->h_word;
+    if (part >= 0) clk.mark(part);
+    if (*total > max_total) return kLbTooLarge;
+    if (int rc = alloc(*total)) return rc;
+    for (int j = 0; j < nl; ++j)
+        if (int rc = launch(j, true)) return rc;
+    return RT_OK;
+}
+
+// The slots' lists and records on the device (lb_build below, which owns the
+// temporaries T): the plan, then three levels of lists — the hyper level of
+// the big slots, the supercells, the cells — and the dcap lists.
+static int lb_lists(rt_ctx* c, int ntr, int n_opaque, const std::vector<const float4*>& cones,
+                    const std::vector<double>& dcov, LbClock& clk, DevScope& T)
+{
+    hipStream_t st = c->stream;
+    const int nl = (int)cones.size();
     // cells of ~1/4 the median cone radius: best of 1-8 on C3 and C5; and
     // no coarser than 128 cells per face edge (small scenes: C2 -3.3%, C4
     // -2.5% against their 16-48, flat from 192 to 512).  An explicit
@@ -1401,248 +1410,125 @@ static int lb_build(rt_ctx* c, int ntr, int n_opaque, const std::vector<const fl
     const bool scale_set = c->opt_lb_scale > 0.0;
     const double scale = scale_set ? c->opt_lb_scale : (ntr > kClusterMinTriangles ? 6.0 : 4.0);
     const int r_min = scale_set ? kLbGroup : RT_LB_RMIN;
-    // Slot j's pieces in the concatenated device arrays: its triangles in
-    // dmin order (perm) and its dcap list (dperm); its supercell counts /
-    // offsets (nsup + 1 words from sob) and cell offsets (ncell + 1 words
-    // from ob: the slot's lb_off) — each slot's last word stays 0 as a
-    // count, so ONE exclusive scan over a whole array gives every slot its
-    // absolute offsets, the last word its end.
-    // Big slots (more than kLbHyperMin triangles) first filter their
-    // triangles per block of kLbHyper x kLbHyper supercells (hob: that
-    // level's counts / offsets, like sob).
-    struct Slot {
-        int R = 16;
-        size_t perm0 = 0, nperm = 0, dperm0 = 0, ndperm = 0, sob = 0, ob = 0, hob = 0;
-        unsigned nsup = 0, ncell = 0, nhyp = 0;
-        int Gp = 0;
-    };
-    constexpr int kLbHyper = 4;
-    constexpr size_t kLbHyperMin = 4096;
-    std::vector<Slot> B((size_t)nl);
-    std::vector<int> perm_all, dperm_all;
-    size_t sob = 0, ob = 0, hob = 0;
-    int* d_perm = nullptr;
-    unsigned* d_soff = nullptr;
-    int* d_slists = nullptr;
-    unsigned* d_hoff = nullptr;
-    int* d_hlists = nullptr;
-    int rc = RT_OK;
-    auto fail = [&](hipError_t e, const char* what) {
-        if (rc == RT_OK) rc = hip_fail(c, e, what);
-    };
-#define LB_TRY(call)                              \
-    do {                                          \
-        hipError_t e_ = (call);                   \
-        if (e_ != hipSuccess) { fail(e_, #call); goto done; } \
-    } while (0)
-    {
-        // 1. the cone records of every slot (c0, c1 per triangle): one sync
-        std::vector<float4> h((size_t)nl * ntr * 2);
-        for (int j = 0; j < nl; ++j)
-            LB_TRY(hipMemcpyAsync(h.data() + (size_t)j * ntr * 2, cones[j], (size_t)ntr * 2 * sizeof(float4),
+    // 1. the cone records of every slot (c0, c1 per triangle): one sync; the
+    // plan (rt_scenehost.h)
+    std::vector<float> h((size_t)nl * ntr * 8);
+    for (int j = 0; j < nl; ++j)
+        HIP_TRY(c, hipMemcpyAsync(h.data() + (size_t)j * ntr * 8, cones[j], (size_t)ntr * 2 * sizeof(float4),
                                   hipMemcpyDeviceToHost, st));
-        LB_TRY(hipStreamSynchronize(st));
-        mark(0);
-        // per slot on its own host thread (independent): cell resolution from
-        // the median cone angle, the triangles in dmin order, the dcap list
-        std::vector<std::vector<int>> perms((size_t)nl), dperms((size_t)nl);
-        auto prep = [&](int j) {
-            Slot& b = B[j];
-            const float4* hj = h.data() + (size_t)j * ntr * 2;
-            std::vector<double> T;
-            std::vector<int>& perm = perms[j];
-            std::vector<int>& dperm = dperms[j];
-            for (int k = 0; k < n_opaque; ++k) {
-                const float4 c0 = hj[2 * k], c1 = hj[2 * k + 1];
-                if (c0.w > 0.0f && c0.w <= 1.0f) T.push_back(std::acos((double)c0.w));
-                if (c0.w > 0.0f && c1.x < (float)dcov[j]) perm.push_back(k);
-                if (!(c1.z >= (float)dcov[j])) dperm.push_back(k);
-            }
-            if (!T.empty()) {
-                std::nth_element(T.begin(), T.begin() + T.size() / 2, T.end());
-                const double med = std::max(T[T.size() / 2], 1e-4);
-                b.R = (int)std::lround(scale / (kLbGroup * med)) * kLbGroup;
-                b.R = std::min(1024, std::max(r_min, b.R));
-            }
-            std::sort(perm.begin(), perm.end(), [&](int x, int y) {
-                return hj[2 * x + 1].x < hj[2 * y + 1].x || (hj[2 * x + 1].x == hj[2 * y + 1].x && x < y);
-            });
-            auto key = [&](int k) { const float z = hj[2 * k + 1].z; return z == z ? z : -INFINITY; };
-            std::sort(dperm.begin(), dperm.end(),
-                      [&](int x, int y) { return key(x) < key(y) || (key(x) == key(y) && x < y); });
-        };
-        if (nl > 1 && (size_t)n_opaque * nl > 20000) {
-            std::vector<std::thread> th;
-            for (int j = 0; j < nl; ++j) th.emplace_back(prep, j);
-            for (auto& t : th) t.join();
-        } else {
-            for (int j = 0; j < nl; ++j) prep(j);
-        }
-        for (int j = 0; j < nl; ++j) {
-            Slot& b = B[j];
-            b.perm0 = perm_all.size();
-            b.nperm = perms[j].size();
-            perm_all.insert(perm_all.end(), perms[j].begin(), perms[j].end());
-            b.dperm0 = dperm_all.size();
-            b.ndperm = dperms[j].size();
-            dperm_all.insert(dperm_all.end(), dperms[j].begin(), dperms[j].end());
-            const unsigned G = (unsigned)(b.R / kLbGroup);
-            b.nsup = 6u * G * G;
-            b.ncell = 6u * (unsigned)b.R * (unsigned)b.R;
-            b.sob = sob;
-            sob += b.nsup + 1;
-            b.ob = ob;
-            ob += b.ncell + 1;
-            if (b.nperm > kLbHyperMin) {
-                b.Gp = (int)((G + kLbHyper - 1) / kLbHyper);
-                b.nhyp = 6u * (unsigned)(b.Gp * b.Gp);
-                b.hob = hob;
-                hob += b.nhyp + 1;
-            }
-        }
-        mark(1);
-        // 2. device arrays; supercell lists (counts, scan, fill)
-        const size_t np = perm_all.size() + dperm_all.size();
-        LB_TRY(hipMalloc(&d_perm, std::max<size_t>(np, 1) * sizeof(int)));
-        if (!perm_all.empty())
-            LB_TRY(hipMemcpyAsync(d_perm, perm_all.data(), perm_all.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        if (!dperm_all.empty())
-            LB_TRY(hipMemcpyAsync(d_perm + perm_all.size(), dperm_all.data(), dperm_all.size() * sizeof(int),
+    HIP_TRY(c, hipStreamSynchronize(st));
+    clk.mark(0);
+    LbPlan P;
+    lb_plan(h.data(), nl, ntr, n_opaque, dcov.data(), scale, r_min, P);
+    clk.mark(1);
+    // 2. device arrays
+    int *d_perm = nullptr, *d_slists = nullptr, *d_hlists = nullptr;
+    unsigned *d_soff = nullptr, *d_hoff = nullptr;
+    const size_t np = P.perm.size() + P.dperm.size();
+    HIP_TRY(c, T.alloc(&d_perm, std::max<size_t>(np, 1) * sizeof(int)));
+    if (!P.perm.empty())
+        HIP_TRY(c, hipMemcpyAsync(d_perm, P.perm.data(), P.perm.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!P.dperm.empty())
+        HIP_TRY(c, hipMemcpyAsync(d_perm + P.perm.size(), P.dperm.data(), P.dperm.size() * sizeof(int),
                                   hipMemcpyHostToDevice, st));
-        LB_TRY(hipMalloc(&d_soff, sob * sizeof(unsigned) + sizeof(unsigned)));
-        LB_TRY(hipMalloc(&c->d_lb_off, ob * sizeof(unsigned) + sizeof(unsigned)));
-        {
-            const int src = ensure_scan(c, scan_scratch(std::max(std::max(sob, ob), hob)));
-            if (src) {
-                rc = src;
-                goto done;
-            }
-        }
-        LB_TRY(hipMemsetAsync(d_soff, 0, sob * sizeof(unsigned), st));
-        LB_TRY(hipMemsetAsync(c->d_lb_off, 0, ob * sizeof(unsigned), st));
-        unsigned long long* tot = nullptr;
-        // 2a. the hyper level of the big slots (counts, scan, fill)
-        if (hob > 0) {
-            LB_TRY(hipMalloc(&d_hoff, hob * sizeof(unsigned) + sizeof(unsigned)));
-            LB_TRY(hipMemsetAsync(d_hoff, 0, hob * sizeof(unsigned), st));
-            for (int j = 0; j < nl; ++j) {
-                const Slot& b = B[j];
-                if (!b.nhyp) continue;
-                hipLaunchKernelGGL(rt_lb_super, dim3(b.nhyp), dim3(256), 0, st, cones[j], ntr, d_perm + b.perm0,
-                                   (int)b.nperm, b.R, (float)dcov[j], nullptr, d_hoff + b.hob, nullptr,
-                                   kLbGroup * kLbHyper, b.Gp, 2e-3, nullptr, nullptr, 1, 1);
-                LB_TRY(hipGetLastError());
-            }
-            LB_TRY(scan_u32(d_hoff, (unsigned)hob, d_hoff, (unsigned long long*)c->d_scan, st, &tot));
-            LB_TRY(hipMemcpyAsync(c->h_word, tot, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            LB_TRY(hipStreamSynchronize(st));
-            const unsigned long long nhl = *c->h_word;
-            if (nhl > 0xFFFFFFF0ull) {
-                c->err = "light buffer too large";
-                goto done;
-            }
-            LB_TRY(hipMalloc(&d_hlists, std::max<size_t>(nhl, 1) * sizeof(int)));
-            for (int j = 0; j < nl; ++j) {
-                const Slot& b = B[j];
-                if (!b.nhyp) continue;
-                hipLaunchKernelGGL(rt_lb_super, dim3(b.nhyp), dim3(256), 0, st, cones[j], ntr, d_perm + b.perm0,
-                                   (int)b.nperm, b.R, (float)dcov[j], d_hoff + b.hob, nullptr, d_hlists,
-                                   kLbGroup * kLbHyper, b.Gp, 2e-3, nullptr, nullptr, 1, 1);
-                LB_TRY(hipGetLastError());
-            }
-        }
-        // 2b. supercells: counts, scan, fill
-        for (int j = 0; j < nl; ++j) {
-            const Slot& b = B[j];
-            hipLaunchKernelGGL(rt_lb_super, dim3(b.nsup), dim3(256), 0, st, cones[j], ntr, d_perm + b.perm0,
-                               (int)b.nperm, b.R, (float)dcov[j], nullptr, d_soff + b.sob, nullptr, kLbGroup,
-                               b.R / kLbGroup, 1e-3, b.nhyp ? d_hoff + b.hob : nullptr, d_hlists, kLbHyper, b.Gp);
-            LB_TRY(hipGetLastError());
-        }
-        LB_TRY(scan_u32(d_soff, (unsigned)sob, d_soff, (unsigned long long*)c->d_scan, st, &tot));
-        LB_TRY(hipMemcpyAsync(c->h_word, tot, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        LB_TRY(hipStreamSynchronize(st));
-        const unsigned long long nsl = *c->h_word;
-        mark(2);
-        if (nsl > 0xFFFFFFF0ull) {
-            c->err = "light buffer too large";
-            goto done;
-        }
-        LB_TRY(hipMalloc(&d_slists, std::max<size_t>(nsl, 1) * sizeof(int)));
-        for (int j = 0; j < nl; ++j) {
-            const Slot& b = B[j];
-            hipLaunchKernelGGL(rt_lb_super, dim3(b.nsup), dim3(256), 0, st, cones[j], ntr, d_perm + b.perm0,
-                               (int)b.nperm, b.R, (float)dcov[j], d_soff + b.sob, nullptr, d_slists, kLbGroup,
-                               b.R / kLbGroup, 1e-3, b.nhyp ? d_hoff + b.hob : nullptr, d_hlists, kLbHyper, b.Gp);
-            LB_TRY(hipGetLastError());
-        }
-        // 3. cell lists (counts, scan into lb_off, fill) and the dcap lists
-        for (int j = 0; j < nl; ++j) {
-            const Slot& b = B[j];
-            hipLaunchKernelGGL(rt_lb_cells, dim3(b.nsup), dim3(256), 0, st, cones[j], ntr, c->d_tri, b.R,
-                               (float)dcov[j], d_soff + b.sob, d_slists, nullptr, c->d_lb_off + b.ob, nullptr);
-            LB_TRY(hipGetLastError());
-        }
-        LB_TRY(scan_u32(c->d_lb_off, (unsigned)ob, c->d_lb_off, (unsigned long long*)c->d_scan, st, &tot));
-        LB_TRY(hipMemcpyAsync(c->h_word, tot, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        LB_TRY(hipStreamSynchronize(st));
-        const unsigned long long total = *c->h_word;
-        mark(3);
-        if (total >= 0xFFFFFFF0ull / 4) {  // entry indices are 32-bit
-            c->err = "light buffer too large";
-            goto done;
-        }
-        LB_TRY(hipMalloc(&c->d_lb_ent, std::max<size_t>(total, 1) * kLbEntF * sizeof(float)));
-        LB_TRY(hipMalloc(&c->d_lb_dcap, std::max<size_t>(dperm_all.size(), 1) * kLbEntF * sizeof(float)));
-        LB_TRY(hipMalloc(&c->d_lb_meta, std::max(nl, 1) * 2 * sizeof(float4)));
-        std::vector<float4> meta((size_t)std::max(nl, 1) * 2);
-        for (int j = 0; j < nl; ++j) {
-            const Slot& b = B[j];
-            hipLaunchKernelGGL(rt_lb_cells, dim3(b.nsup), dim3(256), 0, st, cones[j], ntr, c->d_tri, b.R,
-                               (float)dcov[j], d_soff + b.sob, d_slists, c->d_lb_off + b.ob, nullptr, (float*)c->d_lb_ent);
-            LB_TRY(hipGetLastError());
-            if (b.ndperm) {
-                hipLaunchKernelGGL(rt_lb_dcap, dim3((unsigned)((b.ndperm + 255) / 256)), dim3(256), 0, st, cones[j],
-                                   c->d_tri, d_perm + perm_all.size() + b.dperm0, (int)b.ndperm,
-                                   (float*)c->d_lb_dcap + kLbEntF * b.dperm0);
-                LB_TRY(hipGetLastError());
-            }
-            unsigned obj = (unsigned)b.ob, db = (unsigned)b.dperm0, nd = (unsigned)b.ndperm;
-            float4 m0, m1 = make_float4((float)dcov[j], 0.f, 0.f, 0.f);
-            std::memcpy(&m0.x, &obj, 4);
-            std::memcpy(&m0.y, &db, 4);
-            std::memcpy(&m0.z, &nd, 4);
-            std::memcpy(&m0.w, &b.R, 4);
-            if (j == 0) c->lb_r0 = b.R;
-            meta[2 * j] = m0;
-            meta[2 * j + 1] = m1;
-        }
-        LB_TRY(hipMemcpyAsync(c->d_lb_meta, meta.data(), meta.size() * sizeof(float4), hipMemcpyHostToDevice, st));
-        LB_TRY(hipStreamSynchronize(st));  // meta (host) outlives the copy; the temporaries are freed below
-        c->h_lb_meta = meta;  // (the light records are made from it, light_records)
-        mark(4);
-        c->lb_ready = true;
-        c->lb_entries = total;
+    HIP_TRY(c, T.alloc(&d_soff, P.sob * sizeof(unsigned) + sizeof(unsigned)));
+    HIP_TRY(c, hipMalloc(&c->d_lb_off, P.ob * sizeof(unsigned) + sizeof(unsigned)));
+    if (int rc = ensure_scan(c, scan_scratch(std::max(std::max(P.sob, P.ob), P.hob)))) return rc;
+    HIP_TRY(c, hipMemsetAsync(d_soff, 0, P.sob * sizeof(unsigned), st));
+    HIP_TRY(c, hipMemsetAsync(c->d_lb_off, 0, P.ob * sizeof(unsigned), st));
+    // a level's index lists, a temporary
+    auto ints = [&](int** lists) {
+        return [&T, c, lists](unsigned long long n) -> int {
+            HIP_TRY(c, T.alloc(lists, std::max<size_t>(n, 1) * sizeof(int)));
+            return RT_OK;
+        };
+    };
+    unsigned long long total = 0;
+    // 2a. the hyper level of the big slots: blocks of kLbHyper x kLbHyper supercells
+    if (P.hob > 0) {
+        HIP_TRY(c, T.alloc(&d_hoff, P.hob * sizeof(unsigned) + sizeof(unsigned)));
+        HIP_TRY(c, hipMemsetAsync(d_hoff, 0, P.hob * sizeof(unsigned), st));
+        auto hyper = [&](int j, bool fill) -> int {
+            const LbSlot& b = P.slots[j];
+            if (!b.nhyp) return RT_OK;
+            unsigned* const o = d_hoff + b.hob;
+            hipLaunchKernelGGL(rt_lb_super, dim3(b.nhyp), dim3(256), 0, st, cones[j], ntr, d_perm + b.perm0,
+                               (int)b.nperm, b.R, (float)dcov[j], fill ? o : nullptr, fill ? nullptr : o,
+                               fill ? d_hlists : nullptr, kLbGroup * kLbHyper, b.Gp, 2e-3, nullptr, nullptr, 1, 1);
+            HIP_TRY(c, hipGetLastError());
+            return RT_OK;
+        };
+        if (int rc = lb_level(c, clk, -1, nl, d_hoff, P.hob, 0xFFFFFFF0ull, &total, hyper, ints(&d_hlists))) return rc;
     }
-done:
-#undef LB_TRY
-    if (rc != RT_OK || !c->lb_ready) (void)hipStreamSynchronize(st);
-    hipFree(d_slists);
-    hipFree(d_soff);
-    hipFree(d_hlists);
-    hipFree(d_hoff);
-    hipFree(d_perm);
+    // 2b. supercells, each from its hyper block's list where the slot has one
+    auto super = [&](int j, bool fill) -> int {
+        const LbSlot& b = P.slots[j];
+        unsigned* const o = d_soff + b.sob;
+        hipLaunchKernelGGL(rt_lb_super, dim3(b.nsup), dim3(256), 0, st, cones[j], ntr, d_perm + b.perm0, (int)b.nperm,
+                           b.R, (float)dcov[j], fill ? o : nullptr, fill ? nullptr : o, fill ? d_slists : nullptr,
+                           kLbGroup, b.R / kLbGroup, 1e-3, b.nhyp ? d_hoff + b.hob : nullptr, d_hlists, kLbHyper, b.Gp);
+        HIP_TRY(c, hipGetLastError());
+        return RT_OK;
+    };
+    if (int rc = lb_level(c, clk, 2, nl, d_soff, P.sob, 0xFFFFFFF0ull, &total, super, ints(&d_slists))) return rc;
+    // 3. cell lists (offsets: the slots' lb_off) and, with each slot's fill,
+    // its dcap list
+    auto cells = [&](int j, bool fill) -> int {
+        const LbSlot& b = P.slots[j];
+        unsigned* const o = c->d_lb_off + b.ob;
+        hipLaunchKernelGGL(rt_lb_cells, dim3(b.nsup), dim3(256), 0, st, cones[j], ntr, c->d_tri, b.R, (float)dcov[j],
+                           d_soff + b.sob, d_slists, fill ? o : nullptr, fill ? nullptr : o,
+                           fill ? (float*)c->d_lb_ent : nullptr);
+        HIP_TRY(c, hipGetLastError());
+        if (fill && b.ndperm) {
+            hipLaunchKernelGGL(rt_lb_dcap, dim3((unsigned)((b.ndperm + 255) / 256)), dim3(256), 0, st, cones[j], c->d_tri,
+                               d_perm + P.perm.size() + b.dperm0, (int)b.ndperm,
+                               (float*)c->d_lb_dcap + kLbEntF * b.dperm0);
+            HIP_TRY(c, hipGetLastError());
+        }
+        return RT_OK;
+    };
+    auto buffers = [&](unsigned long long n) -> int {
+        HIP_TRY(c, hipMalloc(&c->d_lb_ent, std::max<size_t>(n, 1) * kLbEntF * sizeof(float)));
+        HIP_TRY(c, hipMalloc(&c->d_lb_dcap, std::max<size_t>(P.dperm.size(), 1) * kLbEntF * sizeof(float)));
+        HIP_TRY(c, hipMalloc(&c->d_lb_meta, std::max(nl, 1) * 2 * sizeof(float4)));
+        return RT_OK;
+    };
+    // (entry indices are 32-bit: four words per entry)
+    if (int rc = lb_level(c, clk, 3, nl, c->d_lb_off, P.ob, 0xFFFFFFF0ull / 4 - 1, &total, cells, buffers)) return rc;
+    // 4. per slot [off base, dcap base, n dcap, R] [dcov 0 0 0]
+    std::vector<float4> meta((size_t)std::max(nl, 1) * 2);
+    for (int j = 0; j < nl; ++j) {
+        const LbSlot& b = P.slots[j];
+        const unsigned words[4] = {(unsigned)b.ob, (unsigned)b.dperm0, (unsigned)b.ndperm, (unsigned)b.R};
+        std::memcpy(&meta[2 * j], words, sizeof words);
+        meta[2 * j + 1] = make_float4((float)dcov[j], 0.f, 0.f, 0.f);
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_lb_meta, meta.data(), meta.size() * sizeof(float4), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));  // meta (host) outlives the copy; the temporaries are freed by the caller
+    c->h_lb_meta = meta;  // (light_records_build makes the light records from it)
+    clk.mark(4);
+    c->lb_r0 = nl > 0 ? P.slots[0].R : 0;
+    c->lb_ready = true;
+    c->lb_entries = total;
+    return RT_OK;
+}
+
+static int lb_build(rt_ctx* c, int ntr, int n_opaque, const std::vector<const float4*>& cones,
+                    const std::vector<double>& dcov)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc;
+    {
+        DevScope T;
+        LbClock clk{c};
+        rc = lb_lists(c, ntr, n_opaque, cones, dcov, clk, T);
+        if (rc != RT_OK) (void)hipStreamSynchronize(c->stream);  // nothing reads the temporaries any more
+    }
     c->lb_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (rc == RT_OK && !c->lb_ready) {  // too large: run without it
-        hipFree(c->d_lb_off);
-        hipFree(c->d_lb_ent);
-        hipFree(c->d_lb_dcap);
-        hipFree(c->d_lb_meta);
-        c->d_lb_off = nullptr;
-        c->d_lb_ent = c->d_lb_dcap = c->d_lb_meta = nullptr;
-        c->err.clear();
-    }
-    return rc;
+    if (rc != kLbTooLarge) return rc;
+    lb_drop(c);  // too large: run without it
+    return RT_OK;
 }
 
 // The occupied-direction bound [a.x a.y a.z cosB] of one light buffer
@@ -1707,311 +1593,109 @@ static unsigned lb_region_build(const unsigned* off, int R, float* out4)
     return cnt;
 }
 
-RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
+// ---- rt_upload_scene's stages, in the order it runs them
+static double ms_since(std::chrono::steady_clock::time_point t)
 {
-    if (!c || !s || s->n_surfaces < 0 || s->n_lights < 0) return RT_E_ARG;
-    if (s->n_surfaces > 0 && (!s->type || !s->geom || !s->material)) return RT_E_ARG;
-    if (s->n_lights > 0 && !s->lights) return RT_E_ARG;
-    if (c->cpu) {
-        c->uploaded = false;
-        const int rc = cpu_upload(&c->cpu_scene, s);
-        if (rc) {
-            c->err = "unknown surface type";
-            return rc;
-        }
-        c->n_surf = s->n_surfaces;
-        c->n_lights = s->n_lights;
-        c->uploaded = true;
-        return RT_OK;
-    }
-    if (!c->stream) return RT_E_STATE;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // nothing in flight may still read the buffers replaced below
-    if (int rc = sync_all(c)) return rc;
-    free_retired(c);
-    const auto tu0 = std::chrono::steady_clock::now();
-    auto since = [](std::chrono::steady_clock::time_point t) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-    };
-    hipStream_t st = c->stream;
-    const int n = s->n_surfaces, nl = s->n_lights;
-    std::vector<float> geom((size_t)std::max(n, 1) * 16, 0.0f), mat((size_t)std::max(n, 1) * 12, 0.0f),
-        lig((size_t)std::max(nl, 1) * 8, 0.0f);
-    bool opaque = true;
-    float kmax = 0.0f, krmax = 0.0f, ktmax = 0.0f;
-    for (int i = 0; i < n; ++i) {
-        const float* g = s->geom + 12 * (size_t)i;
-        const float* m = s->material + 10 * (size_t)i;
-        float* o = &geom[16 * (size_t)i];
-        int kind = s->type[i];
-        if (kind < RT_TRIANGLE || kind > RT_QUADRIC) {
-            c->err = "unknown surface type";
-            return RT_E_ARG;
-        }
-        std::memcpy(&o[0], &kind, sizeof(int));
-        if (kind == RT_TRIANGLE) {
-            const Vec3 p0 = make3(g[0], g[1], g[2]), p1 = make3(g[3], g[4], g[5]), p2 = make3(g[6], g[7], g[8]);
-            const Vec3 e1 = p1 - p0, e2 = p2 - p0;  // Triangle.cpp:135-136
-            o[1] = p0.x; o[2] = p0.y; o[3] = p0.z;
-            o[4] = e1.x; o[5] = e1.y; o[6] = e1.z;
-            o[7] = e2.x; o[8] = e2.y; o[9] = e2.z;
-            o[10] = g[9]; o[11] = g[10]; o[12] = g[11];
-        } else if (kind == RT_PLANE) {
-            o[1] = g[0]; o[2] = g[1]; o[3] = g[2]; o[4] = g[3];
-        } else {
-            o[1] = g[0]; o[2] = g[1]; o[3] = g[2];  // quad
-            o[4] = g[6]; o[5] = g[7]; o[6] = g[8];  // mix
-            o[7] = g[3]; o[8] = g[4]; o[9] = g[5];  // lin
-            o[10] = g[9];
-        }
-        const Color fc = Color{m[0], m[1], m[2]} * m[8];  // colour * Kt
-        o[13] = fc.r; o[14] = fc.g; o[15] = fc.b;
-        opaque = opaque && nonneg_finite(fc.r) && nonneg_finite(fc.g) && nonneg_finite(fc.b);
-        float* q = &mat[12 * (size_t)i];
-        for (int k = 0; k < 10; ++k) q[k] = m[k];
-        if (m[7] > kmax) kmax = m[7];
-        if (m[8] > kmax) kmax = m[8];
-        if (m[7] > krmax) krmax = m[7];
-        if (m[8] > ktmax) ktmax = m[8];
-    }
-    // Per-kind arrays, opaque surfaces first (file order kept inside each class).
-    auto opaque_at = [&](int i) {
-        const float* o = &geom[16 * (size_t)i];
-        return o[13] == 0.0f && o[14] == 0.0f && o[15] == 0.0f;
-    };
-    std::vector<float> tri, pla, qua;
-    std::vector<int> translucent;
-    int n_tri_o = 0, n_pla_o = 0, n_qua_o = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int i = 0; i < n; ++i) {
-            if (opaque_at(i) != (pass == 0)) continue;
-            const float* o = &geom[16 * (size_t)i];
-            float idx;
-            std::memcpy(&idx, &i, sizeof(int));
-            const int kind = s->type[i];
-            if (kind == RT_TRIANGLE) {
-                const float r[12] = {o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], idx, 0.f, 0.f};
-                tri.insert(tri.end(), r, r + 12);
-                n_tri_o += pass == 0;
-            } else if (kind == RT_PLANE) {
-                const float r[8] = {o[1], o[2], o[3], o[4], idx, 0.f, 0.f, 0.f};
-                pla.insert(pla.end(), r, r + 8);
-                n_pla_o += pass == 0;
-            } else {
-                const float r[12] = {o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], idx, 0.f};
-                qua.insert(qua.end(), r, r + 12);
-                n_qua_o += pass == 0;
-            }
-        }
-    }
-    for (int i = 0; i < n; ++i)
-        if (!opaque_at(i)) translucent.push_back(i);
-    // Big lists: cluster order (kd_order) inside the opaque and the
-    // translucent ranges, so 64 consecutive triangles form a compact cluster
-    // for the two-level culling.  The order is free: closest hit is the
-    // lexicographic (t, file index) minimum and opaque shadow tests are any-hit.
-    if (tri.size() / 12 > (size_t)kClusterMinTriangles) cluster_order(tri, n_tri_o);
-    const int cnt_tri = (int)(tri.size() / 12), cnt_pla = (int)(pla.size() / 8), cnt_qua = (int)(qua.size() / 12);
-    const int cnt_translucent = (int)translucent.size();
-    tri.resize(std::max<size_t>(tri.size(), 12));
-    pla.resize(std::max<size_t>(pla.size(), 8));
-    qua.resize(std::max<size_t>(qua.size(), 12));
-    translucent.resize(std::max<size_t>(translucent.size(), 1));
-    for (int j = 0; j < nl; ++j) {
-        const float* l = s->lights + 7 * (size_t)j;
-        float* o = &lig[8 * (size_t)j];
-        o[0] = l[0]; o[1] = l[1]; o[2] = l[2]; o[3] = l[6];
-        o[4] = l[3]; o[5] = l[4]; o[6] = l[5]; o[7] = 0.0f;
-    }
-    hipFree(c->d_geom);
-    hipFree(c->d_mat);
-    hipFree(c->d_lights);
-    hipFree(c->d_tri);
-    hipFree(c->d_plane);
-    hipFree(c->d_quad);
-    hipFree(c->d_translucent);
-    hipFree(c->d_tricam);
-    hipFree(c->d_trisph);
-    hipFree(c->d_cone_cam);
-    hipFree(c->d_cone_light);
-    hipFree(c->d_trinrm);
-    hipFree(c->d_tricoef);
-    hipFree(c->d_clu_cam);
-    hipFree(c->d_clu_light);
-    c->d_tricam = c->d_trisph = c->d_cone_cam = c->d_cone_light = c->d_trinrm = c->d_tricoef = nullptr;
-    c->d_clu_cam = c->d_clu_light = nullptr;
-    c->n_clu = 0;
-    hipFree(c->d_lb_off);
-    hipFree(c->d_lb_ent);
-    hipFree(c->d_lb_dcap);
-    hipFree(c->d_lb_meta);
-    hipFree(c->d_lrec);
-    c->d_lb_off = nullptr;
-    c->d_lb_ent = c->d_lb_dcap = c->d_lb_meta = c->d_lrec = nullptr;
-    c->h_lb_meta.clear();
-    c->h_lrec.clear();
-    c->lb_ready = false;
-    c->lb_levels = 0;
-    c->lb_r0 = 0;
-    c->lb_entries = 0;
-    hipFree(c->d_uni);
-    c->d_uni = nullptr;
-    hipFree(c->d_bvh_node);
-    hipFree(c->d_bvh_tri);
-    hipFree(c->d_skey);
-    c->d_bvh_node = c->d_bvh_tri = nullptr;
-    c->d_skey = nullptr;
-    c->nbin_half = 0;
-    c->bvh_inner = c->bvh_leaves = c->bvh_depth = 0;
-    c->bvh_build_ms = 0.0;
-    c->cb.valid = false;  // buffers are kept (reallocated on demand)
-    c->cam_valid = false;
-    c->lb_build_ms = 0.0;
-    c->d_geom = c->d_mat = c->d_lights = c->d_tri = c->d_plane = c->d_quad = nullptr;
-    c->d_translucent = nullptr;
-    c->uploaded = false;
-    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, bytes);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-    };
-    HIP_TRY(c, up((void**)&c->d_tri, tri.data(), tri.size() * sizeof(float)));
-    HIP_TRY(c, up((void**)&c->d_plane, pla.data(), pla.size() * sizeof(float)));
-    HIP_TRY(c, up((void**)&c->d_quad, qua.data(), qua.size() * sizeof(float)));
-    HIP_TRY(c, up((void**)&c->d_translucent, translucent.data(), translucent.size() * sizeof(int)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_tricam, (tri.size() / 12) * 16 * sizeof(float)));
-    // the bounce-ray BVH: only a scene with a reflective or refractive
-    // surface has bounce rays (Scene.cpp:1779-1823 gate on Kr, Kt > 0)
-    if (kmax > 0.0f && cnt_tri >= RT_BVH_MIN_TRIANGLES && (size_t)cnt_tri <= kBvhMaxTriangles) {
-        const auto tb = std::chrono::steady_clock::now();
-        BvhBuilt B;
-        bvh_build(tri, (size_t)cnt_tri, B);
-        if (B.depth <= kBvhStack) {
-            HIP_TRY(c, up((void**)&c->d_bvh_node, B.nodes.data(), B.nodes.size() * sizeof(float4)));
-            HIP_TRY(c, up((void**)&c->d_bvh_tri, B.tris.data(), B.tris.size() * sizeof(float4)));
-            // the sort bins: triangle at leaf position p -> p / 2 (its
-            // file index is the leaf record's third float4 .y), every other
-            // surface a bin of its own after them
-            std::vector<unsigned> skey((size_t)n, 0u);
-            std::vector<char> is_tri((size_t)n, 0);
-            for (int i = 0; i < cnt_tri; ++i) {
-                int fi;
-                std::memcpy(&fi, &B.tris[3 * (size_t)i + 2].y, sizeof fi);
-                if (fi >= 0 && fi < n) {
-                    skey[(size_t)fi] = (unsigned)i >> 1;
-                    is_tri[(size_t)fi] = 1;
-                }
-            }
-            unsigned nb = ((unsigned)cnt_tri + 1u) >> 1;
-            for (int i = 0; i < n; ++i)
-                if (!is_tri[(size_t)i]) skey[(size_t)i] = nb++;
-            HIP_TRY(c, up((void**)&c->d_skey, skey.data(), skey.size() * sizeof(unsigned)));
-            c->nbin_half = nb;
-            c->bvh_inner = B.inner;
-            c->bvh_leaves = B.leaves;
-            c->bvh_depth = B.depth;
-        }
-        c->bvh_build_ms = since(tb);
-    }
-    // Per triangle (tri[] order), for rt_cone_prepass: the bounding sphere of
-    // the triangle the reference tests (p0, p0 + e1, p0 + e2 with the float
-    // edges; radius measured from the float-rounded centre), the unit normal
-    // and longest edge, and the rounding-bound coefficients gS, gL, rho_cap.
-    // rho_cap = -1: det can be too inexact at the reference's 0.01 gate
-    // (longest edge >~ 110) — never culled.
-    const size_t ntr = tri.size() / 12;
-    std::vector<float> sph(ntr * 4), nrm(ntr * 4), coef(ntr * 4);
-    const double eps = 0x1p-24;
-    for (size_t k = 0; k < ntr; ++k) {
-        const float* r = &tri[12 * k];
-        double p[3][3];
-        for (int a = 0; a < 3; ++a) {
-            p[0][a] = r[a];
-            p[1][a] = (double)r[a] + (double)r[3 + a];
-            p[2][a] = (double)r[a] + (double)r[6 + a];
-        }
-        float ctr[3];
-        for (int a = 0; a < 3; ++a) ctr[a] = (float)((p[0][a] + p[1][a] + p[2][a]) / 3.0);
-        double rad = 0, L2 = 0;
-        for (int q = 0; q < 3; ++q) {
-            double d2 = 0;
-            for (int a = 0; a < 3; ++a) d2 += (p[q][a] - ctr[a]) * (p[q][a] - ctr[a]);
-            rad = std::max(rad, std::sqrt(d2));
-            for (int w = q + 1; w < 3; ++w) {
-                double l2 = 0;
-                for (int a = 0; a < 3; ++a) l2 += (p[q][a] - p[w][a]) * (p[q][a] - p[w][a]);
-                L2 = std::max(L2, l2);
-            }
-        }
-        rad = rad * (1.0 + 1e-9);
-        for (int a = 0; a < 3; ++a) sph[4 * k + a] = ctr[a];
-        sph[4 * k + 3] = std::nextafter((float)rad, INFINITY);
-        const double e1[3] = {r[3], r[4], r[5]}, e2[3] = {r[6], r[7], r[8]};
-        const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2],
-                     nz = e1[0] * e2[1] - e1[1] * e2[0];
-        const double nn = std::sqrt(nx * nx + ny * ny + nz * nz);
-        const double L = std::sqrt(L2) * (1.0 + 1e-9);
-        const double dl = 7.0 * eps * L * L;
-        const double rho_cap = dl < 0.01 ? dl / (0.01 - dl) + 3.0 * eps : INFINITY;
-        const bool fine = nn > 0 && std::isfinite(nn) && rho_cap <= 0.5;
-        const double kk = fine ? 1.0 / (1.0 - rho_cap) : 2.0;
-        nrm[4 * k] = fine ? (float)(nx / nn) : 0.f;
-        nrm[4 * k + 1] = fine ? (float)(ny / nn) : 0.f;
-        nrm[4 * k + 2] = fine ? (float)(nz / nn) : 0.f;
-        nrm[4 * k + 3] = std::nextafter((float)L, INFINITY);
-        coef[4 * k] = fine ? (float)(54.0 * kk * eps * L * L / nn * 1.01) : 0.f;
-        coef[4 * k + 1] = fine ? (float)(21.0 * kk * eps * L * L * L / nn * 1.01) : 0.f;
-        coef[4 * k + 2] = fine ? (float)(rho_cap * 1.01) : -1.0f;
-        coef[4 * k + 3] = fine ? (float)nn : 0.0f;  // |N| = |e1 x e2| (never-hit bound)
-    }
-    sph.resize(std::max<size_t>(sph.size(), 4));
-    nrm.resize(std::max<size_t>(nrm.size(), 4));
-    coef.resize(std::max<size_t>(coef.size(), 4));
-    c->tiny_valid = false;
-    for (auto& q : c->tiny_masks) q.valid = q.pend_valid = false;  // the old scene's triangles
-    if (ntr > 0 && ntr <= (size_t)kTinyMax) {  // the launch-camera path's host records
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+// A host array in a device buffer of its own.
+template <class P, class T>
+static hipError_t up(P** dst, const std::vector<T>& v)
+{
+    const hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(T));
+    if (e != hipSuccess) return e;
+    return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// A slot's first lb_meta record (a light record's third): the base of its
+// cell offsets in lb_off and its resolution R.
+static void lb_meta_words(const float4& m, unsigned& obase, int& R)
+{
+    std::memcpy(&obase, &m.x, 4);
+    std::memcpy(&R, &m.w, 4);
+}
+
+// The per-kind lists and per-triangle records, the buffers of the camera's
+// and the lights' cone records, and the tiny scenes' host copies.
+static int upload_records(rt_ctx* c, const SceneHost& H)
+{
+    const size_t ntr = H.ntr;
+    HIP_TRY(c, up(&c->d_tri, H.tri));
+    HIP_TRY(c, up(&c->d_plane, H.pla));
+    HIP_TRY(c, up(&c->d_quad, H.qua));
+    HIP_TRY(c, up(&c->d_translucent, H.translucent));
+    HIP_TRY(c, hipMalloc((void**)&c->d_tricam, ntr * 16 * sizeof(float)));
+    HIP_TRY(c, up(&c->d_trisph, H.sph));
+    HIP_TRY(c, up(&c->d_trinrm, H.nrm));
+    HIP_TRY(c, up(&c->d_tricoef, H.coef));
+    HIP_TRY(c, hipMalloc((void**)&c->d_cone_cam, ntr * kConeRec * sizeof(float4)));
+    HIP_TRY(c, hipMalloc((void**)&c->d_cone_light, std::max<size_t>(ntr * H.n_lights, 1) * kConeRec * sizeof(float4)));
+    c->h_plane = H.pla;
+    if (ntr <= (size_t)kTinyMax) {  // the launch-camera path's host records
         auto f4 = [](const std::vector<float>& v, size_t n) {
             std::vector<float4> o(n);
             std::memcpy(o.data(), v.data(), n * sizeof(float4));
             return o;
         };
-        c->h_tri = f4(tri, 3 * ntr);
-        c->h_sph = f4(sph, ntr);
-        c->h_nrm = f4(nrm, ntr);
-        c->h_coef = f4(coef, ntr);
-    } else {
-        c->h_tri.clear();
-        c->h_sph.clear();
-        c->h_nrm.clear();
-        c->h_coef.clear();
+        c->h_tri = f4(H.tri, 3 * ntr);
+        c->h_sph = f4(H.sph, ntr);
+        c->h_nrm = f4(H.nrm, ntr);
+        c->h_coef = f4(H.coef, ntr);
     }
-    HIP_TRY(c, up((void**)&c->d_trisph, sph.data(), sph.size() * sizeof(float)));
-    HIP_TRY(c, up((void**)&c->d_trinrm, nrm.data(), nrm.size() * sizeof(float)));
-    HIP_TRY(c, up((void**)&c->d_tricoef, coef.data(), coef.size() * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_cone_cam, std::max<size_t>(ntr, 1) * kConeRec * sizeof(float4)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_cone_light, std::max<size_t>(ntr * nl, 1) * kConeRec * sizeof(float4)));
-    c->upload_parts_ms[0] = since(tu0);
-    const auto tp0 = std::chrono::steady_clock::now();
-    std::vector<double> lb_dcov((size_t)std::max(nl, 0), 0.0);
-    // RT_OPT_DCOV_NEAR / rt_set_far_ladder override the big-list factors
-    // (tests: force lanes into the far buffers and beyond them)
-    const double fac_near = c->opt_dcov_near > 0.0 ? c->opt_dcov_near : RT_DCOV_FACTOR;
-    const std::vector<double> fac_far = c->far_ladder;
-    const double dfac = ntr > (size_t)kClusterMinTriangles ? fac_near : RT_DCOV_FACTOR_SMALL;
-    for (int j = 0; j < nl && ntr > 0; ++j) {
-        const float* l = s->lights + 7 * (size_t)j;
-        // shadow rays are culled up to dfac x the light's farthest triangle
-        double far = 0;
-        for (size_t k = 0; k < ntr; ++k) {
-            double d2 = 0;
-            for (int a = 0; a < 3; ++a) d2 += ((double)sph[4 * k + a] - l[a]) * ((double)sph[4 * k + a] - l[a]);
-            far = std::max(far, std::sqrt(d2) + sph[4 * k + 3]);
-        }
-        hipLaunchKernelGGL(rt_cone_prepass, dim3((unsigned)((ntr + 255) / 256)), dim3(256), 0, st, c->d_tri, c->d_trisph,
-                           c->d_trinrm, c->d_tricoef, (int)ntr, l[0], l[1], l[2], 0, (float)(dfac * far),
-                           c->d_cone_light + kConeRec * ntr * j, (float4*)nullptr);
-        HIP_TRY(c, hipGetLastError());
-        lb_dcov[j] = (double)(float)(dfac * far);
+    return RT_OK;
+}
+
+static int upload_bvh(rt_ctx* c, const SceneHost& H)
+{
+    c->bvh_build_ms = H.bvh_build_ms;
+    if (!H.has_bvh) return RT_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, up(&c->d_bvh_node, H.bvh.nodes));
+    HIP_TRY(c, up(&c->d_bvh_tri, H.bvh.tris));
+    HIP_TRY(c, up(&c->d_skey, H.skey));
+    c->nbin_half = H.nbin_half;
+    c->bvh_inner = H.bvh.inner;
+    c->bvh_leaves = H.bvh.leaves;
+    c->bvh_depth = H.bvh.depth;
+    c->bvh_build_ms += ms_since(t0);
+    return RT_OK;
+}
+
+// Light j's cone records for shadow rays up to `distance` from it.
+static int launch_light_cones(rt_ctx* c, const SceneHost& H, int j, float distance, float4* out)
+{
+    const float* l = &H.lig[8 * (size_t)j];
+    hipLaunchKernelGGL(rt_cone_prepass, dim3((unsigned)((H.ntr + 255) / 256)), dim3(256), 0, c->stream, c->d_tri,
+                       c->d_trisph, c->d_trinrm, c->d_tricoef, (int)H.ntr, l[0], l[1], l[2], 0, distance, out,
+                       (float4*)nullptr);
+    HIP_TRY(c, hipGetLastError());
+    return RT_OK;
+}
+
+// Shadow rays are culled up to this factor of a light's farthest triangle.
+// RT_OPT_DCOV_NEAR overrides the big lists' (tests: force lanes into the far
+// buffers and beyond them).
+static double dcov_factor(const rt_ctx* c, const SceneHost& H)
+{
+    if (H.ntr <= (size_t)kClusterMinTriangles) return RT_DCOV_FACTOR_SMALL;
+    return c->opt_dcov_near > 0.0 ? c->opt_dcov_near : RT_DCOV_FACTOR;
+}
+
+// The lights' prepasses: every light's cone records for its distance
+// dcov[j], then the cluster records of a big list or the union records of a
+// small one ([camera (filled when the camera is set)] [light 0] ...).
+static int light_prepasses(rt_ctx* c, const SceneHost& H, std::vector<double>& dcov)
+{
+    hipStream_t st = c->stream;
+    const size_t ntr = H.ntr;
+    const int nl = H.n_lights, n_tri_o = H.n_tri_opaque;
+    const double dfac = dcov_factor(c, H);
+    dcov.assign((size_t)nl, 0.0);
+    for (int j = 0; j < nl; ++j) {
+        const float d = (float)(dfac * H.far[(size_t)j]);
+        if (int rc = launch_light_cones(c, H, j, d, c->d_cone_light + kConeRec * ntr * j)) return rc;
+        dcov[(size_t)j] = (double)d;
     }
     if (ntr > (size_t)kClusterMinTriangles) {
         c->n_clu = (int)((ntr + 63) / 64);
@@ -2023,146 +1707,172 @@ RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
                                c->d_clu_light + 2 * (size_t)c->n_clu * j, 64);
             HIP_TRY(c, hipGetLastError());
         }
+        return RT_OK;
     }
-    if (ntr > 0 && ntr <= (size_t)kClusterMinTriangles) {
-        // union records: [camera (filled when the camera is set)] [light 0] ...
-        HIP_TRY(c, hipMalloc((void**)&c->d_uni, (size_t)(nl + 1) * 2 * sizeof(float4)));
-        for (int j = 0; j < nl && n_tri_o > 0; ++j) {
-            hipLaunchKernelGGL(rt_cluster_prepass, dim3(1), dim3(64), 0, st, c->d_cone_light + kConeRec * ntr * j,
-                               n_tri_o, 1, c->d_uni + 2 * (1 + (size_t)j), n_tri_o);  // one wave
-            HIP_TRY(c, hipGetLastError());
-        }
-        if (n_tri_o == 0) {  // no opaque triangle: nothing for shadow rays to walk ("never" record)
-            std::vector<float4> nev((size_t)nl * 2);
-            for (int j = 0; j < nl; ++j) {
-                nev[2 * j] = make_float4(0.f, 0.f, 0.f, 2.0f);
-                nev[2 * j + 1] = make_float4(INFINITY, 0.f, INFINITY, 0.f);
-            }
-            if (nl) HIP_TRY(c, hipMemcpyAsync(c->d_uni + 2, nev.data(), nev.size() * sizeof(float4), hipMemcpyHostToDevice, st));
-            HIP_TRY(c, hipStreamSynchronize(st));  // nev outlives the copy
-        }
+    HIP_TRY(c, hipMalloc((void**)&c->d_uni, (size_t)(nl + 1) * 2 * sizeof(float4)));
+    for (int j = 0; j < nl && n_tri_o > 0; ++j) {
+        hipLaunchKernelGGL(rt_cluster_prepass, dim3(1), dim3(64), 0, st, c->d_cone_light + kConeRec * ntr * j, n_tri_o,
+                           1, c->d_uni + 2 * (1 + (size_t)j), n_tri_o);  // one wave
+        HIP_TRY(c, hipGetLastError());
     }
-    // the sequence slots (rt_render_sequence_async): per-camera records of
-    // their own; the union records' light part is the scene's
+    if (n_tri_o == 0) {  // no opaque triangle: nothing for shadow rays to walk ("never" record)
+        std::vector<float4> nev((size_t)nl * 2);
+        for (int j = 0; j < nl; ++j) {
+            nev[2 * j] = make_float4(0.f, 0.f, 0.f, 2.0f);
+            nev[2 * j + 1] = make_float4(INFINITY, 0.f, INFINITY, 0.f);
+        }
+        if (nl) HIP_TRY(c, hipMemcpyAsync(c->d_uni + 2, nev.data(), nev.size() * sizeof(float4), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipStreamSynchronize(st));  // nev outlives the copy
+    }
+    return RT_OK;
+}
+
+// The sequence slots (rt_render_sequence_async): per-camera records of
+// their own; the union records' light part is the scene's.
+static int alloc_seq_slots(rt_ctx* c, const SceneHost& H)
+{
+    const size_t ntr = H.ntr, uni = (size_t)(H.n_lights + 1) * 2 * sizeof(float4);
     for (auto& q : c->seq) {
-        hipFree(q.tricam);
-        hipFree(q.cone_cam);
-        hipFree(q.clu_cam);
-        hipFree(q.uni);
-        const rt_ctx::CamBuf keep = q.cb;  // its buffers are kept (resized on demand)
-        q = rt_ctx::CamSlot{};
-        q.cb = keep;
-        q.cb.valid = false;
-        if (ntr == 0) continue;
         // every triangle's camera record: the camera-buffer walk reads them
         HIP_TRY(c, hipMalloc((void**)&q.tricam, ntr * 4 * sizeof(float4)));
         HIP_TRY(c, hipMalloc((void**)&q.cone_cam, ntr * kConeRec * sizeof(float4)));
         if (c->n_clu > 0) HIP_TRY(c, hipMalloc((void**)&q.clu_cam, (size_t)c->n_clu * 4 * sizeof(float4)));
         if (c->d_uni) {
-            HIP_TRY(c, hipMalloc((void**)&q.uni, (size_t)(nl + 1) * 2 * sizeof(float4)));
-            HIP_TRY(c, hipMemcpyAsync(q.uni, c->d_uni, (size_t)(nl + 1) * 2 * sizeof(float4), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(c, hipMalloc((void**)&q.uni, uni));
+            HIP_TRY(c, hipMemcpyAsync(q.uni, c->d_uni, uni, hipMemcpyDeviceToDevice, c->stream));
         }
     }
-    HIP_TRY(c, hipStreamSynchronize(st));
-    c->upload_parts_ms[1] = since(tp0);
-    const auto tl0 = std::chrono::steady_clock::now();
-    const int lbm = c->opt_light_buffer;  // built only where launch() will use it
-    if (ntr > 0 && nl > 0 && n_tri_o > 0 && opaque && (lbm == 1 || (lbm == 2 && ntr > (size_t)kClusterMinTriangles))) {
-        std::vector<const float4*> cones;
-        for (int j = 0; j < nl; ++j) cones.push_back(c->d_cone_light + kConeRec * ntr * j);
-        std::vector<double> dcov = lb_dcov;
-        // Big lists: a far buffer per light, its cone records built for
-        // RT_DCOV_FACTOR_FAR x the farthest triangle, for the lanes beyond the
-        // near buffer's dcov (else the per-lane loop over every triangle).
-        // (one level per factor: slots level * n_lights + light)
-        float4* d_cone_far = nullptr;
-        const size_t nlev = ntr > (size_t)kClusterMinTriangles ? fac_far.size() : 0;
-        if (nlev > 0) {
-            HIP_TRY(c, hipMalloc((void**)&d_cone_far, nlev * ntr * nl * kConeRec * sizeof(float4)));
-            for (size_t v = 0; v < nlev; ++v)
-                for (int j = 0; j < nl; ++j) {
-                    const float* l = s->lights + 7 * (size_t)j;
-                    const double dfar = lb_dcov[j] / dfac * fac_far[v];
-                    float4* out = d_cone_far + kConeRec * ntr * (v * nl + j);
-                    hipLaunchKernelGGL(rt_cone_prepass, dim3((unsigned)((ntr + 255) / 256)), dim3(256), 0, st,
-                                       c->d_tri, c->d_trisph, c->d_trinrm, c->d_tricoef, (int)ntr, l[0], l[1], l[2], 0,
-                                       (float)dfar, out, (float4*)nullptr);
-                    HIP_TRY(c, hipGetLastError());
-                    cones.push_back(out);
-                    dcov.push_back((double)(float)dfar);
-                }
-        }
-        const int rc = lb_build(c, (int)ntr, n_tri_o, cones, dcov);
-        hipFree(d_cone_far);
-        if (rc) return rc;
-        c->lb_levels = c->lb_ready ? 1 + (int)nlev : 0;
-    }
-    c->upload_parts_ms[2] = since(tl0);
-    HIP_TRY(c, hipMalloc(&c->d_geom, geom.size() * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&c->d_mat, mat.size() * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&c->d_lights, lig.size() * sizeof(float)));
-    HIP_TRY(c, hipMemcpy(c->d_geom, geom.data(), geom.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_mat, mat.data(), mat.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_lights, lig.data(), lig.size() * sizeof(float), hipMemcpyHostToDevice));
-    // The launch-camera kernels' light records (rt_shade.h): per light its
-    // lights[] pair, its first buffer's lb_meta pair and that buffer's
-    // occupied-direction bound (lb_region_build, from the buffers' cell
-    // offsets read back once) in 64 bytes,
-    // [x y z I] [r g b dcov] [off base, dcap base, n dcap, R] [a.x a.y a.z cosB];
-    // then the same records with [0 0 0 -2] ("always look", RT_OPT_LB_REGION 0).
-    c->h_plane = pla;
-    if (c->lb_ready && ntr <= (size_t)kTinyMax && c->h_lb_meta.size() >= 2 * (size_t)nl) {
-        std::vector<float4> lr((size_t)kLightRec * nl * 2);
-        // the lights' first buffers' offsets (consecutive slices of lb_off): one copy
-        std::vector<unsigned> off;
-        size_t lo = SIZE_MAX, hi = 0;
+    return RT_OK;
+}
+
+// The light buffers, built only where launch() will use them.  Big lists: a
+// ladder of far buffers per light after the near one, level v's cone records
+// built for far_ladder[v] x the farthest triangle, for the lanes beyond the
+// level before (else the per-lane loop over every triangle): slots
+// level * n_lights + light.
+static int lb_ladder(rt_ctx* c, const SceneHost& H, const std::vector<double>& near_dcov)
+{
+    const size_t ntr = H.ntr;
+    const int nl = H.n_lights, lbm = c->opt_light_buffer;
+    const bool big = ntr > (size_t)kClusterMinTriangles;
+    if (!(nl > 0 && H.n_tri_opaque > 0 && H.shadow_split && (lbm == 1 || (lbm == 2 && big)))) return RT_OK;
+    std::vector<const float4*> cones;
+    for (int j = 0; j < nl; ++j) cones.push_back(c->d_cone_light + kConeRec * ntr * j);
+    std::vector<double> dcov = near_dcov;
+    DevScope T;
+    float4* d_cone_far = nullptr;
+    const double dfac = dcov_factor(c, H);
+    const size_t nlev = big ? c->far_ladder.size() : 0;
+    if (nlev > 0) HIP_TRY(c, T.alloc(&d_cone_far, nlev * ntr * nl * kConeRec * sizeof(float4)));
+    for (size_t v = 0; v < nlev; ++v)
         for (int j = 0; j < nl; ++j) {
-            unsigned obase;
-            int R;
-            std::memcpy(&obase, &c->h_lb_meta[2 * j].x, 4);
-            std::memcpy(&R, &c->h_lb_meta[2 * j].w, 4);
-            if (R <= 0) continue;
-            lo = std::min(lo, (size_t)obase);
-            hi = std::max(hi, (size_t)obase + 6 * (size_t)R * R + 1);
+            const double dfar = near_dcov[(size_t)j] / dfac * c->far_ladder[v];
+            float4* out = d_cone_far + kConeRec * ntr * (v * nl + j);
+            if (int rc = launch_light_cones(c, H, j, (float)dfar, out)) return rc;
+            cones.push_back(out);
+            dcov.push_back((double)(float)dfar);
         }
-        if (hi > lo) {
-            off.resize(hi - lo);
-            HIP_TRY(c, hipMemcpy(off.data(), c->d_lb_off + lo, off.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-        }
-        for (int j = 0; j < nl; ++j) {
-            const float* l = &lig[8 * (size_t)j];
-            lr[kLightRec * j] = make_float4(l[0], l[1], l[2], l[3]);
-            lr[kLightRec * j + 1] = make_float4(l[4], l[5], l[6], c->h_lb_meta[2 * j + 1].x);
-            lr[kLightRec * j + 2] = c->h_lb_meta[2 * j];
-            unsigned obase;
-            int R;
-            std::memcpy(&obase, &c->h_lb_meta[2 * j].x, 4);
-            std::memcpy(&R, &c->h_lb_meta[2 * j].w, 4);
-            float rg[4] = {0.f, 0.f, 0.f, -2.0f};
-            if (R > 0) lb_region_build(off.data() + (obase - lo), R, rg);
-            lr[kLightRec * j + 3] = make_float4(rg[0], rg[1], rg[2], rg[3]);
-            for (int q = 0; q < 3; ++q) lr[kLightRec * (nl + j) + q] = lr[kLightRec * j + q];
-            lr[kLightRec * (nl + j) + 3] = make_float4(0.f, 0.f, 0.f, -2.0f);
-        }
-        c->h_lrec.assign(lr.begin(), lr.begin() + (size_t)kLightRec * nl);
-        HIP_TRY(c, hipMalloc(&c->d_lrec, lr.size() * sizeof(float4)));
-        HIP_TRY(c, hipMemcpy(c->d_lrec, lr.data(), lr.size() * sizeof(float4), hipMemcpyHostToDevice));
+    if (int rc = lb_build(c, (int)ntr, H.n_tri_opaque, cones, dcov)) return rc;
+    c->lb_levels = c->lb_ready ? 1 + (int)nlev : 0;
+    return RT_OK;
+}
+
+// The surface, material and light records in file order (what shading reads).
+static int upload_surfaces(rt_ctx* c, const SceneHost& H)
+{
+    HIP_TRY(c, up(&c->d_geom, H.geom));
+    HIP_TRY(c, up(&c->d_mat, H.mat));
+    HIP_TRY(c, up(&c->d_lights, H.lig));
+    return RT_OK;
+}
+
+// The launch-camera kernels' light records (rt_shade.h), tiny scenes with a
+// light buffer: per light its lights[] pair, its first buffer's lb_meta pair
+// and that buffer's occupied-direction bound (lb_region_build, from the
+// buffers' cell offsets read back once) in 64 bytes,
+// [x y z I] [r g b dcov] [off base, dcap base, n dcap, R] [a.x a.y a.z cosB];
+// then the same records with [0 0 0 -2] ("always look", RT_OPT_LB_REGION 0).
+static int light_records_build(rt_ctx* c, const SceneHost& H)
+{
+    const int nl = H.n_lights;
+    if (!(c->lb_ready && H.ntr <= (size_t)kTinyMax && c->h_lb_meta.size() >= 2 * (size_t)nl)) return RT_OK;
+    // the lights' first buffers' offsets (consecutive slices of lb_off): one copy
+    std::vector<unsigned> off, obase((size_t)nl);
+    std::vector<int> R((size_t)nl);
+    size_t lo = SIZE_MAX, hi = 0;
+    for (int j = 0; j < nl; ++j) {
+        lb_meta_words(c->h_lb_meta[2 * j], obase[j], R[j]);
+        if (R[j] <= 0) continue;
+        lo = std::min(lo, (size_t)obase[j]);
+        hi = std::max(hi, (size_t)obase[j] + 6 * (size_t)R[j] * R[j] + 1);
     }
-    c->n_surf = n;
-    c->n_lights = nl;
-    c->n_tri = cnt_tri;
-    c->n_plane = cnt_pla;
-    c->n_quad = cnt_qua;
-    c->n_tri_opaque = n_tri_o;
-    c->n_plane_opaque = n_pla_o;
-    c->n_quad_opaque = n_qua_o;
-    c->n_translucent = cnt_translucent;
-    c->shadow_split = opaque ? 1 : 0;
-    c->k_max = kmax;
-    c->kr_max = krmax;
-    c->kt_max = ktmax;
+    if (hi > lo) {
+        off.resize(hi - lo);
+        HIP_TRY(c, hipMemcpy(off.data(), c->d_lb_off + lo, off.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    }
+    std::vector<float4> lr((size_t)kLightRec * nl * 2);
+    for (int j = 0; j < nl; ++j) {
+        const float* l = &H.lig[8 * (size_t)j];
+        lr[kLightRec * j] = make_float4(l[0], l[1], l[2], l[3]);
+        lr[kLightRec * j + 1] = make_float4(l[4], l[5], l[6], c->h_lb_meta[2 * j + 1].x);
+        lr[kLightRec * j + 2] = c->h_lb_meta[2 * j];
+        float rg[4] = {0.f, 0.f, 0.f, -2.0f};
+        if (R[j] > 0) lb_region_build(off.data() + (obase[j] - lo), R[j], rg);
+        lr[kLightRec * j + 3] = make_float4(rg[0], rg[1], rg[2], rg[3]);
+        for (int q = 0; q < 3; ++q) lr[kLightRec * (nl + j) + q] = lr[kLightRec * j + q];
+        lr[kLightRec * (nl + j) + 3] = make_float4(0.f, 0.f, 0.f, -2.0f);
+    }
+    c->h_lrec.assign(lr.begin(), lr.begin() + (size_t)kLightRec * nl);
+    HIP_TRY(c, up(&c->d_lrec, lr));
+    return RT_OK;
+}
+
+static int cpu_upload_scene(rt_ctx* c, const rt_scene_flat* s)
+{
+    c->uploaded = false;
+    const int rc = cpu_upload(&c->cpu_scene, s);
+    if (rc) {
+        c->err = "unknown surface type";
+        return rc;
+    }
+    c->n_surf = s->n_surfaces;
+    c->n_lights = s->n_lights;
     c->uploaded = true;
-    c->upload_parts_ms[3] = since(tu0);
+    return RT_OK;
+}
+
+RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
+{
+    if (!c || !s || s->n_surfaces < 0 || s->n_lights < 0) return RT_E_ARG;
+    if (s->n_surfaces > 0 && (!s->type || !s->geom || !s->material)) return RT_E_ARG;
+    if (s->n_lights > 0 && !s->lights) return RT_E_ARG;
+    if (c->cpu) return cpu_upload_scene(c, s);
+    if (!c->stream) return RT_E_STATE;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // nothing in flight may still read the buffers replaced below
+    if (int rc = sync_all(c)) return rc;
+    free_retired(c);
+    const auto tu0 = std::chrono::steady_clock::now();
+    SceneHost H;
+    if (!scene_host_build(s, H, c->err)) return RT_E_ARG;  // (the context is as it was)
+    scene_drop(c);
+    if (int rc = upload_records(c, H)) return rc;
+    if (int rc = upload_bvh(c, H)) return rc;
+    c->upload_parts_ms[0] = ms_since(tu0);
+    const auto tp0 = std::chrono::steady_clock::now();
+    std::vector<double> dcov;  // per light: its (first) buffer's distance
+    if (int rc = light_prepasses(c, H, dcov)) return rc;
+    if (int rc = alloc_seq_slots(c, H)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->upload_parts_ms[1] = ms_since(tp0);
+    const auto tl0 = std::chrono::steady_clock::now();
+    if (int rc = lb_ladder(c, H, dcov)) return rc;
+    c->upload_parts_ms[2] = ms_since(tl0);
+    if (int rc = upload_surfaces(c, H)) return rc;
+    if (int rc = light_records_build(c, H)) return rc;
+    static_cast<SceneCounts&>(*c) = H;  // publish the counts
+    c->uploaded = true;
+    c->upload_parts_ms[3] = ms_since(tu0);
     return RT_OK;
 }
 
@@ -3706,8 +3416,8 @@ RT_EXPORT int rt_debug_lb_info(rt_ctx* c, double* out, int n)
     HIP_TRY(c, hipMemcpy(meta.data(), c->d_lb_meta, meta.size() * sizeof(float4), hipMemcpyDeviceToHost));
     for (int j = 0; j < c->n_lights && 3 + 3 * j + 2 < n; ++j) {
         int R;
-        unsigned nd;
-        std::memcpy(&R, &meta[2 * j].w, 4);
+        unsigned obase, nd;
+        lb_meta_words(meta[2 * j], obase, R);
         std::memcpy(&nd, &meta[2 * j].z, 4);
         out[3 + 3 * j] = R;
         out[4 + 3 * j] = nd;
@@ -3735,8 +3445,7 @@ RT_EXPORT int rt_debug_lb_region(rt_ctx* c, double* out, int n)
     for (int j = 0; j < nl && e == hipSuccess; ++j) {
         unsigned obase;
         int R;
-        std::memcpy(&obase, &c->h_lrec[kLightRec * j + 2].x, 4);
-        std::memcpy(&R, &c->h_lrec[kLightRec * j + 2].w, 4);
+        lb_meta_words(c->h_lrec[kLightRec * j + 2], obase, R);
         if (R <= 0) continue;
         hipLaunchKernelGGL(rt_lb_region_check, dim3((unsigned)((6 * R * R + 255) / 256)), dim3(256), 0, c->stream,
                            c->d_lb_off + obase, R, c->h_lrec[kLightRec * j + 3], d_cnt + 2 * j);
@@ -3767,8 +3476,7 @@ RT_EXPORT int rt_debug_lb_offsets(rt_ctx* c, int light, unsigned* out, int n)
     }
     unsigned obase;
     int R;
-    std::memcpy(&obase, &c->h_lb_meta[2 * (size_t)light].x, 4);
-    std::memcpy(&R, &c->h_lb_meta[2 * (size_t)light].w, 4);
+    lb_meta_words(c->h_lb_meta[2 * (size_t)light], obase, R);
     if (R <= 0 || n != 6 * R * R + 1) return RT_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemcpy(out, c->d_lb_off + obase, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));

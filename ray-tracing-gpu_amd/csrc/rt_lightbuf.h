@@ -7,6 +7,7 @@
 #define RT_AMD_RT_LIGHTBUF_H
 
 #include "rt_cull.h"
+#include "rt_dims.h"
 
 #pragma clang fp contract(off)
 
@@ -29,7 +30,7 @@ namespace rt {
 // is not valid up to dcov (dcap < dcov, or never culled) are in a separate
 // per-light list sorted by dcap, tested by the lanes with dist > dcap — the
 // per-lane predicate light_reach, split in two.
-constexpr int kLbGroup = 16;  // cells per supercell edge (two-level build)
+// (kLbGroup, the cells per supercell edge of the two-level build: rt_dims.h)
 // Light-buffer entry: 10 floats (40 B, 8-byte aligned) — [p0, key] [e1,
 // e2.x] [e2.y, e2.z] (48 B in round 2: C3 313 -> 269 MB per frame).
 constexpr int kLbEntF = 10;  // floats per light-buffer entry

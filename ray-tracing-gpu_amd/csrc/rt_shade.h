@@ -915,7 +915,7 @@ __device__ __forceinline__ Color shade_local(const SceneDev& S, const Mat& m, co
 
 // ---- the launch-camera kernels' light loop (rt_trace_tiny, rt_cull.h TinyHead)
 // Light-shade record, 64 bytes, one per light of the small-list light buffer
-// (built at upload, light_records): what shade_local's light-buffer loop
+// (built at upload, light_records_build): what shade_local's light-buffer loop
 // reads per light from lights[] and lb_meta[] — four loads behind three
 // waits — as one 16-dword scalar load.
 //   [x y z I] [r g b dcov] [off base, dcap base, n dcap, R (int bits)] [a.x a.y a.z cosB]

@@ -518,3 +518,42 @@ def test_camera_buffer_covers_only_the_ranks_rows(which, heightfield_path):
         a = (q * 8 + 3) * 16
         e = min(1080, a + 16)
         assert bits_equal(part[q * 16: q * 16 + (e - a)], full[a:e])
+
+
+def test_reupload_matches_fresh_context(tmp_path):
+    """One context re-used across scene classes — a clustered list with a
+    BVH and the far ladder, a tiny scene, the empty scene, the clustered one
+    again — drops and rebuilds everything an upload owns: each frame, the
+    light-buffer summary and the BVH summary equal a fresh context's."""
+    import ctypes
+
+    from wf_scenes import wf_dat
+
+    big = tmp_path / "split_1026.dat"
+    big.write_text(wf_dat("split", 1026))
+    empty = tmp_path / "empty.dat"
+    empty.write_text("")
+    cases = [(str(big), 3), (scene(2), 0), (str(empty), 0), (str(big), 3)]
+    L = rt_amd.lib()
+    for fn in (L.rt_debug_lb_info, L.rt_debug_bvh_info):
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+
+    def state(c, path, depth):
+        s = rt_amd.Scene(path, 64, 48, depth)
+        c.upload(s)
+        img = c.render_float(s.frame)
+        lb, bvh = (ctypes.c_double * 30)(), (ctypes.c_double * 5)()
+        assert L.rt_debug_lb_info(c._h, lb, 30) == 0 and L.rt_debug_bvh_info(c._h, bvh, 5) == 0
+        return img, list(lb[:2]) + list(lb[3:]), list(bvh[:4])  # without their milliseconds
+
+    shared = rt_amd.Context(0)
+    got = [state(shared, p, d) for p, d in cases]
+    want = [state(rt_amd.Context(0), p, d) for p, d in cases]
+    for (img, lb, bvh), (wimg, wlb, wbvh) in zip(got, want):
+        assert bits_equal(img, wimg)
+        assert lb == wlb and bvh == wbvh
+    assert bits_equal(got[0][0], got[3][0])
+    # the cases are what they are meant to be: ladder + BVH, a light buffer without a BVH, nothing
+    assert got[0][1][0] == 1.0 and got[0][2][0] == 1.0
+    assert got[1][1][0] == 1.0 and got[1][2][0] == 0.0
+    assert got[2][1][0] == 0.0 and got[2][2][0] == 0.0

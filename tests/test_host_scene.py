@@ -143,3 +143,26 @@ def rt_amd_oracle_dump(path):
 def test_bad_resolution():
     with pytest.raises(rt_amd.RtError):
         rt_amd.Scene(scene(1), 0, 8)
+
+
+def test_scene_host_build_under_asan_ubsan(tmp_path):
+    """The host half of rt_upload_scene (csrc/rt_scenehost.h: scene_host_build
+    and lb_plan, the functions the library compiles) in a stand-alone host
+    program built with AddressSanitizer and UBSan: generated scenes at every
+    size where a branch changes and values that break the arithmetic, checked
+    for the properties tools/upload/scene_host_check.cpp lists."""
+    import subprocess
+
+    from conftest import REPO
+
+    exe = tmp_path / "scene_host_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-ffp-contract=off", "-fno-fast-math",
+                    "-I", os.path.join(REPO, "ray-tracing-gpu_amd", "csrc"), "-I", os.path.join(REPO, "include"),
+                    os.path.join(REPO, "tools", "upload", "scene_host_check.cpp"), "-o", str(exe)],
+                   check=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "scene_host_check: ok" in r.stdout
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
