@@ -461,8 +461,10 @@ struct TinyHead {
     float bg[3];
     int height;
     int row_begin, row_end, band_rows, band_count;
-    int band_index, flags, n, masked;  // n, masked: TinyCam's
-    unsigned* mask;                    // TinyCam's mask (tiles_x below)
+    int band_index;
+    unsigned tm_all;  // the mask of a tile without one: every listed triangle, (1 << n) - 1
+    int n, masked;    // TinyCam's
+    unsigned* mask;   // TinyCam's mask (tiles_x below)
     int tiles_x, n_plane;
     float4 plane[kTinyPlanes];  // [n cst]
     float pnum[kTinyPlanes];    // n . O + cst
@@ -484,6 +486,7 @@ struct TinyHead {
     StatsDev* stats;
     int n_lights, n_tri, n_tri_opaque, n_plane_opaque;
     int n_quad, n_quad_opaque, n_translucent, shadow_split;
+    int flags;  // read at the end of a counting launch only
 };
 struct TinyLaunch {
     TinyHead h;
@@ -509,6 +512,7 @@ inline void tiny_head_fill(TinyHead& H, const FrameDev& F, const SceneDev& S, co
     H.band_rows = F.band_rows, H.band_count = F.band_count, H.band_index = F.band_index;
     H.flags = F.flags;
     H.n = T.n, H.masked = T.masked, H.mask = T.mask, H.tiles_x = T.tiles_x;
+    H.tm_all = T.n >= 32 ? ~0u : (1u << T.n) - 1u;
     H.n_plane = S.n_plane;
     // the planes' camera-ray constants, hit_plane's n . O + cst in float
     // (this file is built without contraction, host and device)
@@ -565,6 +569,24 @@ __device__ __forceinline__ unsigned tiny_tile_mask(int n, const TinyLane& L, con
     const bool keep = ((int)(threadIdx.x & 63) < n) & (a.x >= L.q[1].z) & (a.y >= L.q[1].w) & (b.x >= L.q[3].z) &
                       (b.y >= L.q[3].w);
     return (unsigned)__ballot(keep);
+}
+
+// camera_dir for the launch-camera kernels: the same operations, the length
+// and its reciprocal behind one domain dispatch (rt_fastmath.h sqrt_recip_w).
+// A copy, to be kept in step with camera_dir by hand: with the direction in
+// a helper that both call, the compiler schedules the 180 kernels that call
+// camera_dir differently (tried; same values, other instruction order), and
+// those kernels' code is to stay what it was measured as.
+__device__ __forceinline__ Vec3 camera_dir_tiny(const FrameDev& F, int pxc, int pyc)
+{
+    const Vec3 d0 = make3((2 * pxc * F.inv_w - 1) * F.half_w, (2 * pyc * F.inv_h - 1) * F.half_h, -1.0f);
+    Mat4 M;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) M.m[i >> 2][i & 3] = F.orient[i];
+    const Vec3 dm = d0 * M;
+    float len, inv;
+    sqrt_recip_w(dm.x * dm.x + dm.y * dm.y + dm.z * dm.z, len, inv);
+    return len > kEps ? dm * inv : make3(0.f, 0.f, 0.f);
 }
 
 // The launch record's planes as the device functions take them.

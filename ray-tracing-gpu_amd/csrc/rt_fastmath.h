@@ -80,4 +80,21 @@ __device__ __forceinline__ float sqrt_w(float x)
     return sqrt_cr(x);
 }
 
+// s = RN(sqrt(x)) and r = RN(1/s) behind ONE dispatch, for a length and its
+// reciprocal (a normalisation).  sqrt_w(x) then recip_w(s) return the
+// correctly rounded values on whichever side of their dispatches the wave
+// falls, and x in [2^-100, 2^100] puts s in [2^-50, 2^50], inside the
+// reciprocal's domain: so the second test is implied by the first, and the
+// IEEE side here returns the same bits for every x (0, Inf and NaN included).
+__device__ __forceinline__ void sqrt_recip_w(float x, float& s, float& r)
+{
+    if (__builtin_expect(__any(!in_sqrt_domain(x)), 0)) {
+        s = sqrtf(x);
+        r = 1.0f / s;
+        return;
+    }
+    s = sqrt_cr(x);
+    r = rcp_nr(s);
+}
+
 }  // namespace rt

@@ -475,7 +475,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     F.height = H.height;
     F.row_begin = H.row_begin, F.row_end = H.row_end;
     F.band_rows = H.band_rows, F.band_count = H.band_count, F.band_index = H.band_index;
-    F.flags = H.flags;
     int tn = H.n, masked = H.masked, tiles_x = H.tiles_x;
     unsigned* const mask = H.mask;
     TinyPlanes PL;
@@ -486,6 +485,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
         PL.idx[k] = H.pidx[k];
     }
     int n_plane = H.n_plane;
+    unsigned tm = H.tm_all;  // no masks: every listed triangle
     RT_PIN4(F.cam[0], F.cam[1], F.cam[2], F.width);
 #pragma unroll
     for (int i = 0; i < 4; ++i) RT_PIN4(F.orient[4 * i], F.orient[4 * i + 1], F.orient[4 * i + 2], F.half_w);
@@ -496,7 +496,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
 #pragma unroll
     for (int k = 0; k < kTinyPlanes; ++k) {
         RT_PIN4(PL.a[k].x, PL.a[k].y, PL.a[k].z, PL.a[k].w);
-        RT_PIN4(PL.num[k], PL.idx[k], tn, masked);
+        RT_PIN4(PL.num[k], PL.idx[k], tm, masked);
     }
 
     const int lane = threadIdx.x & 63;
@@ -514,7 +514,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     // the full frame (the masks hold for its lanes' clamped pixels)
     const int tile = (py0 & 7) == 0 ? (py0 >> 3) * tiles_x + bx : -1;
     const bool tiled = masked && tile >= 0;
-    unsigned tm = tn >= 32 ? ~0u : (1u << tn) - 1u;  // no masks: every listed triangle
     if constexpr ((WAVE & 64) == 0)
         if (tiled) tm = mask[tile];  // wave-uniform (scalar) load, waited for at the triangles
     TinyLane tl;
@@ -530,7 +529,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     // dropped) so edge waves stay whole
     const int pxc = px < F.width ? px : F.width - 1;
     const int pyc = py < rend ? py : rend - 1;
-    const Vec3 D = camera_dir(F, pxc, pyc);
+    const Vec3 D = camera_dir_tiny(F, pxc, pyc);
     const Vec3 O = make3(F.cam[0], F.cam[1], F.cam[2]);
     cnt.primary = valid ? 1u : 0u;
     unsigned tmask = 0;
@@ -594,7 +593,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     if constexpr ((WAVE & 128) != 0)
         if (lane == 0 && tiled) mask[tile] = tmask;
     tile_prof_flush(cnt);
-    if (COUNT && (F.flags & RT_FLAG_STATS)) tile_tally(cnt, H.stats, true);  // (every lane runs)
+    if (COUNT && (H.flags & RT_FLAG_STATS)) tile_tally(cnt, H.stats, true);  // (every lane runs)
 }
 
 // Compiled bounce-stack capacities.  The host picks the smallest one that

@@ -924,11 +924,33 @@ __device__ __forceinline__ Color shade_local(const SceneDev& S, const Mat& m, co
 // light d has fl(d . a) >= cosB (cosB = -2: no bound, 2: no entry at all).
 constexpr int kLightRec = 4;  // float4 per record
 
+// shadow_plane_hit inside a loop over the lights (`pass`: the light's index).
+// The plane's value at P, n . P + cst, is the same for every light and is
+// kept as one vector register across the loop; the empty asm ties it to the
+// pass, so its two sign tests are compares in the pass.  Left to itself the
+// compiler also hoists the tests, as lane masks: four SGPR pairs for two
+// planes, spilled to VGPR lanes and read back in every pass.
+__device__ __forceinline__ bool shadow_plane_hit_pass(const float4 a, const Vec3 P, const Vec3 L, float dist, int pass)
+{
+    const Vec3 n = make3(a.x, a.y, a.z);
+    const float vd = dot(n, L);
+    float num = dot(n, P) + a.w;
+    asm("" : "+v"(num) : "s"(pass));
+    const bool maybe = (fabsf(vd) > kEps) & (((num < 0) & (vd > 0)) | ((num > 0) & (vd < 0))) &
+                       !(fabsf(num) < 0.0099f * fabsf(vd));
+    if (!__any(maybe)) return false;
+    const float t = -num / vd;
+    return (fabsf(vd) > kEps) & (t > kEps) & (t < dist);
+}
+
 // shadow_opaque_lb<false> (one light's shadow rays against the opaque
 // surfaces through the light's buffer) with the wave-uniform inputs where the
 // launch-camera kernel holds them: the slot's meta from the light's record,
 // the first kTinyPlanes opaque planes from the launch record (in SGPRs
-// across the lights: no load per light).  In the one-cell walk and the dcap
+// across the lights: no load per light; shadow_plane_hit_pass).  The plane
+// section has no exit of its own: once every lane is occluded each later
+// section stops at its first `__any`, and nothing is counted on the way.
+// In the one-cell walk and the dcap
 // list an entry's 40 bytes are loaded together and the dmin / dcap gate is
 // applied to the loaded key: one round trip per entry instead of two.  The
 // gates' outcomes, the tests run and their order are shadow_opaque_lb's, so
@@ -945,13 +967,14 @@ __device__ __forceinline__ void shadow_opaque_tiny(const SceneDev& S, const Tiny
 #pragma unroll
     for (int k = 0; k < kTinyPlanes; ++k) {
         if (k < S.n_plane_opaque) {
-            if (!__any(!occ)) return;
-            ++cnt.pla;
-            occ |= shadow_plane_hit(PL.a[k], P, L, dist);
+            if (__any(!occ)) {
+                ++cnt.pla;
+                occ |= shadow_plane_hit_pass(PL.a[k], P, L, dist, l);
+            }
         }
     }
     for (int k = kTinyPlanes; k < S.n_plane_opaque; ++k) {
-        if (!__any(!occ)) return;
+        if (!__any(!occ)) break;
         ++cnt.pla;
         occ |= shadow_plane_hit(S.plane[2 * k], P, L, dist);
     }
@@ -1096,25 +1119,36 @@ __device__ __forceinline__ Color shade_local_tiny(const SceneDev& S, const TinyP
                                                   Counters& cnt, bool active)
 {
     Color res = m.color * m.ka;
-    for (int li = 0; li < S.n_lights; ++li) {
-        const float4* r = lrec + kLightRec * li;
+    const float4* r = lrec;  // the light's record (a running pointer)
+    for (int li = 0; li < S.n_lights; ++li, r += kLightRec) {
         const float4 l0 = r[0], l1 = r[1], m0 = r[2], rg = r[3];
         const Vec3 Lr = make3(l0.x, l0.y, l0.z) - P;
         const bool gate = active & (dot(Lr, N) > 0);  // Scene.cpp:1756, unnormalised
-        const float dist = sqrt_w(Lr.x * Lr.x + Lr.y * Lr.y + Lr.z * Lr.z);
-        const Vec3 L = Lr * recip_w(dist);
+        float dist, inv;
+        sqrt_recip_w(Lr.x * Lr.x + Lr.y * Lr.y + Lr.z * Lr.z, dist, inv);
+        const Vec3 L = Lr * inv;
         cnt.shadow += gate;
         bool occ = !gate;
         RT_MARK(cnt, 2);
-        shadow_opaque_tiny(S, PL, m0, rg, l1.w, li, P, L, dist, occ, cnt);
+        // T: the scene as this pass reads it, S with the counts the pass
+        // branches on tied to the pass: a scalar compare where each is used,
+        // not a lane mask per comparison carried (and spilled) across the
+        // lights.  This and shadow_plane_hit_pass steer the compiler's
+        // hoisting and spilling and change no value; what they buy depends on
+        // the compiler, so after a ROCm update count the timed instance again
+        // (tools/isa_classes.py: lane_spill 20 against 62 without them).
+        SceneDev T = S;
+        asm("" : "+s"(T.n_plane_opaque), "+s"(T.n_quad_opaque), "+s"(T.n_translucent), "+s"(T.n_tri_opaque)
+            : "s"(li));
+        shadow_opaque_tiny(T, PL, m0, rg, l1.w, li, P, L, dist, occ, cnt);
         RT_MARK(cnt, 7);
         if (gate) {
             Color F{0.0f, 0.0f, 0.0f};
             if (!occ) {  // translucent surfaces, file order
                 F = Color{1.0f, 1.0f, 1.0f};
-                for (int q = 0; q < S.n_translucent; ++q) {
+                for (int q = 0; q < T.n_translucent; ++q) {
                     Color fc;
-                    if (shadow_hit_record(S.geom + 4 * S.translucent[q], P, L, dist, fc, cnt)) F *= fc;
+                    if (shadow_hit_record(T.geom + 4 * T.translucent[q], P, L, dist, fc, cnt)) F *= fc;
                 }
             }
             add_light(res, m, l0, l1, N, L, D, F);  // reads l1's colour only
