@@ -639,7 +639,7 @@ __device__ __forceinline__ int closest_hit_camera_tiny(const SceneDev& S, const 
         const float4* r = rec + 8 * j + 4;
         const float4 d = r[3];
         if (!__any((bi < 0) | !(bt < d.z))) break;
-        camera_tri(r[0], r[1], r[2], d, D, bt, bi, cnt);
+        camera_tri<true>(r[0], r[1], r[2], d, D, bt, bi, cnt);
     }
     best_t = bt;
     return bi;

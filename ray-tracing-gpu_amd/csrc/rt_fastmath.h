@@ -86,15 +86,23 @@ __device__ __forceinline__ float sqrt_w(float x)
 // falls, and x in [2^-100, 2^100] puts s in [2^-50, 2^50], inside the
 // reciprocal's domain: so the second test is implied by the first, and the
 // IEEE side here returns the same bits for every x (0, Inf and NaN included).
+// The fast pair is computed first and overwritten behind the unlikely branch:
+// the fast side then runs one conditional branch, not taken, and the IEEE
+// expansion lies out of line.  (Written with two returns, as the dispatches
+// above, the launch-camera kernels ran two or three branches on the fast
+// side: a flag set on that path and tested again before the join.)  The fast
+// sequences have no side effect on an operand outside their domain; their
+// values are dropped there.
 __device__ __forceinline__ void sqrt_recip_w(float x, float& s, float& r)
 {
+    float fs = sqrt_cr(x);
+    float fr = rcp_nr(fs);
     if (__builtin_expect(__any(!in_sqrt_domain(x)), 0)) {
-        s = sqrtf(x);
-        r = 1.0f / s;
-        return;
+        fs = sqrtf(x);
+        fr = 1.0f / fs;
     }
-    s = sqrt_cr(x);
-    r = rcp_nr(s);
+    s = fs;
+    r = fr;
 }
 
 }  // namespace rt

@@ -337,6 +337,17 @@ __device__ __forceinline__ float recip_det(float det)
     if (__builtin_expect(__any(need_ieee), 0)) return 1.0f / det;
     return rcp_nr(det);
 }
+// recip_det for the launch-camera kernels: the same value for every det, the
+// fast one first and the division behind the unlikely branch (one conditional
+// branch on the fast side, as sqrt_recip_w).
+__device__ __forceinline__ float recip_det_tiny(float det)
+{
+    const float a = fabsf(det);
+    const bool need_ieee = !(a <= 0x1p125f) & !(a < kEps);
+    float inv = rcp_nr(det);
+    if (__builtin_expect(__any(need_ieee), 0)) inv = 1.0f / det;
+    return inv;
+}
 
 }  // namespace rt
 #endif  // RT_AMD_RT_LAYOUT_H

@@ -59,6 +59,29 @@ __device__ __forceinline__ int lb_cell(const Vec3 d, int R)
     return (face * R + j) * R + i;
 }
 
+// lb_cell with the face chosen by selects (compares and v_cndmask, no exec
+// region), for the launch-camera kernels: the same three comparisons in the
+// same order (fx, else fy, else z), so the same integer for every d, the
+// `>=` ties, -0.0 and NaN components included.
+__device__ __forceinline__ int lb_cell_sel(const Vec3 d, int R)
+{
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    const bool fx = (ax >= ay) & (ax >= az);
+    const bool fy = ay >= az;  // read only where !fx
+    const float m = fx ? ax : (fy ? ay : az);
+    const float s = fx ? d.x : (fy ? d.y : d.z);  // the face's own component
+    const float a = fx ? d.y : (fy ? d.z : d.x);
+    const float b = fx ? d.z : (fy ? d.x : d.y);
+    const int face = (fx ? 0 : (fy ? 2 : 4)) + (s >= 0.0f ? 0 : 1);
+    const float inv = __builtin_amdgcn_rcpf(m);
+    const float h = 0.5f * (float)R;
+    int i = (int)floorf((a * inv + 1.0f) * h);
+    int j = (int)floorf((b * inv + 1.0f) * h);
+    i = min(max(i, 0), R - 1);
+    j = min(max(j, 0), R - 1);
+    return (face * R + j) * R + i;
+}
+
 __host__ __device__ __forceinline__ void lb_face_dir(int face, double u, double v, double* o)
 {
     switch (face) {

@@ -128,12 +128,16 @@ struct TriU {
     float inv, u;
     bool ok;
 };
+// TINY: the launch-camera kernels' form of the reciprocal's dispatch
+// (recip_det_tiny: the same value).
+template <bool TINY = false>
 __device__ __forceinline__ TriU tri_u(const Vec3 p0, const Vec3 e1, const Vec3 e2, const Vec3 O, const Vec3 D)
 {
     TriU r;
     r.P = cross(D, e2);
     const float det = dot(e1, r.P);
-    r.inv = recip_det(det);
+    if constexpr (TINY) r.inv = recip_det_tiny(det);
+    else r.inv = recip_det(det);
     r.S = O - p0;
     r.u = dot(r.S, r.P) * r.inv;
     r.ok = !(fabsf(det) < kEps) & !((r.u < 0) | (r.u > 1));
@@ -202,7 +206,8 @@ __device__ __forceinline__ int closest_hit(const SceneDev& S, const Vec3 O, cons
 }
 
 // One camera-ray triangle test: exact u first, the rest only if some lane of
-// the wave is inside the u bounds.
+// the wave is inside the u bounds.  (TINY: as tri_u.)
+template <bool TINY = false>
 __device__ __forceinline__ void camera_tri(const float4 a, const float4 b, const float4 c, const float4 d,
                                            const Vec3 D, float& bt, int& bi, Counters& cnt)
 {
@@ -211,7 +216,9 @@ __device__ __forceinline__ void camera_tri(const float4 a, const float4 b, const
     const Vec3 Sv = make3(b.z, b.w, c.x), Q = make3(c.y, c.z, c.w);
     const Vec3 P = cross(D, e2);
     const float det = dot(e1, P);
-    const float inv = recip_det(det);
+    float inv;
+    if constexpr (TINY) inv = recip_det_tiny(det);
+    else inv = recip_det(det);
     const float u = dot(Sv, P) * inv;
     const bool okU = !(fabsf(det) < kEps) & !((u < 0) | (u > 1));
     if (!__any(okU)) return;

@@ -960,6 +960,13 @@ __device__ __forceinline__ bool shadow_plane_hit_pass(const float4 a, const Vec3
 // the lookup and both walks (each behind a wave-uniform branch).  (The same
 // code with the lookup and the walks inside one `if (any lane looks)` block
 // measured 4.5% slower on C2: more lane-mask bookkeeping on the scalar pipe.)
+// Exec regions the result does not need are written out of this function:
+// the cell comes from lb_cell_sel (selects) inside the lookup's wave-uniform
+// branch, together with the first looking lane's cell and the one-cell vote;
+// in the one-cell walk and the dcap list, whose entries are wave-uniform,
+// every lane runs the triangle test and `act` / `need` gate the vote and the
+// result (the region behind `if (!__any(act)) break;` cannot be empty).  The
+// reciprocals are recip_det_tiny's (tri_u<true>): one branch on the fast side.
 __device__ __forceinline__ void shadow_opaque_tiny(const SceneDev& S, const TinyPlanes& PL, const float4 m0,
                                                    const float4 rg, float dcov, int l, const Vec3 P, const Vec3 L,
                                                    float dist, bool& occ, Counters& cnt)
@@ -985,13 +992,18 @@ __device__ __forceinline__ void shadow_opaque_tiny(const SceneDev& S, const Tiny
     const bool use = cand & !occ & (dist <= dcov) & (R > 0);
     const Vec3 dl = -L;
     const bool look = use & (dot(dl, make3(rg.x, rg.y, rg.z)) >= rg.w);
-    const int cell = look ? lb_cell(dl, R) : 0;
+    const unsigned long long bu = __ballot(look);
+    int cell = 0, cf = 0;
+    bool one_cell = false;
+    if (bu) {  // wave-uniform: the cell, the first looking lane's, and whether all share it
+        const int cell_all = lb_cell_sel(dl, R);
+        cell = look ? cell_all : 0;
+        cf = __builtin_amdgcn_readlane(cell, (int)__builtin_ctzll(bu));
+        one_cell = __all(!look | (cell == cf));
+    }
     RT_MARK(cnt, 3);
     // one cell for every lane that looks: its list by scalar loads
     // (lb_slot); else each lane walks its own cell's list
-    const unsigned long long bu = __ballot(look);
-    const int cf = bu ? __builtin_amdgcn_readlane(cell, (int)__builtin_ctzll(bu)) : 0;
-    const bool one_cell = bu != 0 && __all(!look | (cell == cf));
     unsigned e = 0, end = 0;
     if (bu) {
         if (one_cell) RT_EV(cnt, 0);
@@ -1008,13 +1020,13 @@ __device__ __forceinline__ void shadow_opaque_tiny(const SceneDev& S, const Tiny
             if (!__any(act)) break;
             ++cnt.tri;
             RT_EV(cnt, 4);
-            if (act) {
+            {  // every lane runs the test (the entry is wave-uniform); act gates its result
                 const Vec3 e1 = make3(c1.x, c1.y, c1.z), e2 = make3(c1.w, c2.x, c2.y);
-                const TriU u = tri_u(make3(c0.x, c0.y, c0.z), e1, e2, P, L);
-                if (__any(u.ok)) {
+                const TriU u = tri_u<true>(make3(c0.x, c0.y, c0.z), e1, e2, P, L);
+                if (__any(act & u.ok)) {
                     float t;
                     const bool ok = tri_vt(u, e1, e2, L, t);
-                    occ |= ok & (t > kEps) & (t < dist);
+                    occ |= act & ok & (t > kEps) & (t < dist);
                 }
             }
         }
@@ -1047,7 +1059,7 @@ __device__ __forceinline__ void shadow_opaque_tiny(const SceneDev& S, const Tiny
             RT_EVN(cnt, 7, (unsigned)__popcll(__ballot(go)));
             if (go) {
                 const Vec3 e1 = make3(c1.x, c1.y, c1.z), e2 = make3(c1.w, c2.x, c2.y);
-                const TriU u = tri_u(make3(c0.x, c0.y, c0.z), e1, e2, P, L);
+                const TriU u = tri_u<true>(make3(c0.x, c0.y, c0.z), e1, e2, P, L);
                 if (__any(u.ok)) {
                     float t;
                     const bool ok = tri_vt(u, e1, e2, L, t);
@@ -1066,13 +1078,13 @@ __device__ __forceinline__ void shadow_opaque_tiny(const SceneDev& S, const Tiny
         if (!__any(need)) break;
         ++cnt.tri;
         RT_EV(cnt, 5);
-        if (need) {
+        {  // as in the one-cell walk: need gates the result only
             const Vec3 e1 = make3(r1.x, r1.y, r1.z), e2 = make3(r1.w, r2.x, r2.y);
-            const TriU u = tri_u(make3(r0.x, r0.y, r0.z), e1, e2, P, L);
-            if (__any(u.ok)) {
+            const TriU u = tri_u<true>(make3(r0.x, r0.y, r0.z), e1, e2, P, L);
+            if (__any(need & u.ok)) {
                 float t;
                 const bool ok = tri_vt(u, e1, e2, L, t);
-                occ |= ok & (t > kEps) & (t < dist);
+                occ |= need & ok & (t > kEps) & (t < dist);
             }
         }
     }
