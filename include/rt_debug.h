@@ -120,6 +120,14 @@ int rt_debug_lb_region_build(const unsigned* off, int R, double* out5);
 int rt_debug_row_chunks(int width, int rows, int band_rows, int px_bytes, int ss, int wf, int host_out,
                         double host_chunk_mb, double ss_chunk_rows, int* bounds, int cap);
 
+/* The tile words a tiny-scene (launch-camera) render stored for hip_stream
+ * (NULL: the synchronous renders' stream) read back (synchronous): the first
+ * n words, tile = tile_row * ceil(width / 8) + tile_col over the full frame's
+ * 8 x 8 tiles.  Bits 0-19: the tile's triangle mask; bits 20 + 2 l and
+ * 21 + 2 l: light l's class for l < 6 (0 run the light's shadow pass, 1 lit,
+ * 2 dark).  RT_E_STATE where the stream holds no stored words of n tiles. */
+int rt_debug_tiny_words(rt_ctx*, void* hip_stream, unsigned* out, int n);
+
 #ifdef RT_PROF
 /* Only in a library built with -DRT_PROF (tools/prof_sections.py,
  * tools/prof_tiles.py): per-section shader-clock totals and event counts

@@ -306,6 +306,10 @@ static const TinyCam& tiny_prepare(rt_ctx* c, const rt_frame* f)
 // a moving C2 frame 7% (A/B) —, its next frame on the stream computes and
 // stores them, its later frames read them.  A hipGraph capture computes them
 // (its replays recompute: no buffer).  Sets T.mask.
+// The storing frame (mode 2) also writes each tile's light classes into the
+// word's bits from 20 up (rt_cull.h), which the reading frames (mode 0) use to
+// skip shadow passes; they live and die with the masks: the same key, the
+// same buffer, dropped by the same upload.
 // Buffers are found by the stream's handle, which a destroyed stream's
 // successor may reuse: the storing kernel is followed by an event
 // (tiny_masks_stored) that a reader waits for while it has not passed.  At

@@ -417,7 +417,21 @@ __device__ __forceinline__ int closest_hit_camera_list(const SceneDev& S, int ti
 // kernel itself — lane j tests triangle j, one ballot —, the second also
 // stores it (bit 128, rt_camhost.h tiny_masks); its later frames on that
 // stream read it (one scalar load).
+// The stored word: bits 0-19 the mask; bits 20 + 2 li and 21 + 2 li light
+// li's class for the tile, li < kTinyClassLights (a later light has none):
+//   0  run the light's pass (anything unknown; a tile that was not shaded)
+//   1  lit: the storing frame's opaque shadow pass (shadow_opaque_tiny) left
+//      no gated lane occluded (so too where no lane is gated)
+//   2  dark: it left every lane occluded
+// A reading frame has the storing frame's camera, frame shape and scene
+// (cb_key_of; an upload drops every stored word), so each of its lanes
+// computes what that frame's lane computed and the pass would end the same:
+// it is skipped (rt_shade.h shade_local_tiny).  Counted renders ignore the
+// classes.
 constexpr int kTinyMax = 20;
+constexpr int kTinyClassShift = 20, kTinyClassLights = 6;
+static_assert(kTinyMax <= 20, "the tile word's bits from 20 up are the light classes");
+static_assert(kTinyMax <= kTinyClassShift && kTinyClassShift + 2 * kTinyClassLights <= 32, "the tile word is 32 bits");
 struct TinyCam {
     int n;       // listed triangles (never-hit ones left out)
     int masked;  // 1: tile masks hold (rows aligned to the tile grid); 0: test every listed triangle

@@ -551,6 +551,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     Color c = bg;
     float t;
     RT_MARK(cnt, 0);
+    // the word's light classes (rt_cull.h kTinyClassShift): read with the
+    // stored word, gathered by the storing frame, neither by a camera's first
+    // frame.  A counted render runs every pass (its counters are the general
+    // kernels'); a wave without a tile has tm_all's zero bits there.
+    constexpr int CLS = (WAVE & 128) != 0 ? 2 : ((WAVE & 64) == 0 && !COUNT) ? 1 : 0;
+    unsigned cls = 0;
+    if constexpr ((WAVE & 64) == 0) {
+        if constexpr (CLS == 1) cls = tm >> kTinyClassShift;
+        tm &= (1u << kTinyClassShift) - 1u;
+    }
     const int idx = closest_hit_camera_tiny(S, PL, L.rec, tm, O, D, t, cnt);
     RT_MARK(cnt, 1);
     // Lanes that miss (or lie outside the frame) stay in step through the
@@ -571,7 +581,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
             N = hit_normal(S, sidx, O, D, t);
         }
         const Vec3 P = O + t * D;
-        const Color cl = shade_local_tiny(S, PL, H.lrec, m, P, N, D, cnt, hit & valid);
+        const Color cl = shade_local_tiny<CLS>(S, PL, H.lrec, m, P, N, D, cnt, hit & valid, cls);
         c = hit ? cl : bg;
     }
     if (valid) {
@@ -589,9 +599,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     }
     // the tile's mask for its camera's later frames on this stream (WAVE
     // bit 128), stored last: at the top of the kernel the store's
-    // completion held up the loads behind it (A/B: C2 -2.8%, C4 -2.5%)
+    // completion held up the loads behind it (A/B: C2 -2.8%, C4 -2.5%).
+    // Above the mask's 20 bits, the light classes the shading gathered (0
+    // where the tile was not shaded).
     if constexpr ((WAVE & 128) != 0)
-        if (lane == 0 && tiled) mask[tile] = tmask;
+        if (lane == 0 && tiled) mask[tile] = tmask | cls << kTinyClassShift;
     tile_prof_flush(cnt);
     if (COUNT && (H.flags & RT_FLAG_STATS)) tile_tally(cnt, H.stats, true);  // (every lane runs)
 }
@@ -3589,6 +3601,25 @@ RT_EXPORT int rt_debug_cb_verify(rt_ctx* c, unsigned long long* out)
     out[1] = h[1];
     out[2] = (unsigned long long)std::count(flags.begin(), flags.end(), 0u);
     return rc;
+}
+
+// Diagnostic (include/rt_debug.h): the tile words (rt_cull.h: mask and light
+// classes) a launch-camera render stored for `stream` (tiny_masks; NULL: the
+// synchronous renders' stream), the first n of them.  Synchronous.
+RT_EXPORT int rt_debug_tiny_words(rt_ctx* c, void* stream, unsigned* out, int n)
+{
+    if (!c || !out || n < 0) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = sync_all(c)) return rc;
+    const hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    for (const auto& q : c->tiny_masks)
+        if (q.stream == st && q.valid && q.d && (size_t)n <= q.cap) {
+            HIP_TRY(c, hipMemcpy(out, q.d, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));
+            return RT_OK;
+        }
+    c->err = "no stored tile words of that size for the stream";
+    return RT_E_STATE;
 }
 
 // Diagnostic (include/rt_debug.h): the last rt_upload_scene's host wall

@@ -1126,12 +1126,24 @@ __device__ __forceinline__ void shadow_opaque_tiny(const SceneDev& S, const Tiny
 // launch-camera kernels: the light's record is one load at the top of its
 // pass.  The host sends these kernels only scenes with shadow_split set (the
 // light buffer is built for no others).
+// CLS, cls: the tile's light classes (rt_cull.h kTinyClassShift), two bits
+// per light from light 0 up.  CLS 0: none.  CLS 2 (the storing frame): each
+// pass's class is gathered into cls from what the pass computed anyway.
+// CLS 1 (the later frames): a pass whose class is 1 or 2 takes the opaque
+// shadow result the storing frame's same pass ended with, which is then one
+// value per lane without a test: lit leaves occ = !gate (a gated lane's occ
+// ended false, an ungated lane's started true and is only ever or-ed into),
+// dark sets every lane's.  Same camera, frame and scene, so the same P, N
+// and gate lane for lane: exact by determinism.  Class 0, and every light
+// from kTinyClassLights up, runs the pass.
+template <int CLS>
 __device__ __forceinline__ Color shade_local_tiny(const SceneDev& S, const TinyPlanes& PL, const float4* lrec,
                                                   const Mat& m, const Vec3 P, const Vec3 N, const Vec3 D,
-                                                  Counters& cnt, bool active)
+                                                  Counters& cnt, bool active, unsigned& cls)
 {
     Color res = m.color * m.ka;
     const float4* r = lrec;  // the light's record (a running pointer)
+    unsigned rest = cls;  // CLS 1: this and the later lights' classes
     for (int li = 0; li < S.n_lights; ++li, r += kLightRec) {
         const float4 l0 = r[0], l1 = r[1], m0 = r[2], rg = r[3];
         const Vec3 Lr = make3(l0.x, l0.y, l0.z) - P;
@@ -1152,7 +1164,23 @@ __device__ __forceinline__ Color shade_local_tiny(const SceneDev& S, const TinyP
         SceneDev T = S;
         asm("" : "+s"(T.n_plane_opaque), "+s"(T.n_quad_opaque), "+s"(T.n_translucent), "+s"(T.n_tri_opaque)
             : "s"(li));
-        shadow_opaque_tiny(T, PL, m0, rg, l1.w, li, P, L, dist, occ, cnt);
+        if constexpr (CLS == 1) {
+            const unsigned k = rest & 3u;  // wave-uniform
+            rest >>= 2;
+            occ |= k == 2u;
+            // the pass out of line (most tiles have a class): without the
+            // hint the instance holds 26 scalars in vector lanes, with the
+            // result set in an else branch 41, this way 15 (the parent 18;
+            // tools/isa_classes.py lane_spill)
+            if (__builtin_expect(k == 0, 0)) shadow_opaque_tiny(T, PL, m0, rg, l1.w, li, P, L, dist, occ, cnt);
+        } else {
+            shadow_opaque_tiny(T, PL, m0, rg, l1.w, li, P, L, dist, occ, cnt);
+        }
+        if constexpr (CLS == 2) {
+            // lit before dark: a pass without a gated lane is both, stored lit
+            const unsigned k = !__any(gate & occ) ? 1u : __all(occ) ? 2u : 0u;
+            if (li < kTinyClassLights) cls |= k << (2 * li);
+        }
         RT_MARK(cnt, 7);
         if (gate) {
             Color F{0.0f, 0.0f, 0.0f};
