@@ -38,23 +38,27 @@ __device__ __forceinline__ void aov_store(T v, T* p)
 // One wave per 8 x 8 tile: trace_tile's frame geometry (slab / band row
 // mapping, lanes outside the frame on a clamped pixel so that edge waves stay
 // whole for the wave-level culling; their result is dropped).
-// WAVE: 0 no per-camera state, every surface per lane (closest_hit<false>:
-//         closest_hit_primary<0> would read the camera's cone records, which
-//         do not exist for the scenes that render here — the launch-camera
-//         scenes and those without triangles; culling never changes a
-//         winner, so the hit is the same);
-//       1 / 9 wave culling, without / with the camera buffer;
-//       2 / 10 clustered two-level culling, without / with the camera buffer
-//         (the dynamic LDS window of the colour kernels' staged walks).
+// WAVE (rt_variant.h), the culling and the camera buffer only:
+//   kCullNone: no per-camera state, every surface per lane
+//     (closest_hit<false>: closest_hit_primary<kCullNone> would read the
+//     camera's cone records, which do not exist for the scenes that render
+//     here — the launch-camera scenes and those without triangles; culling
+//     never changes a winner, so the hit is the same);
+//   kCullWave: wave culling, without / with kCamBuf (labels 1 / 9);
+//   kCullClustered: clustered two-level culling, without / with kCamBuf
+//     (labels 2 / 10; the dynamic LDS window of the colour kernels' staged
+//     walks).
 // out_t / out_id / out_n: planar (1, 1, 3 values per pixel), each may be null.
 template <int WAVE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
-    (WAVE & 2) ? RT_WAVES_PER_EU_BIG : RT_WAVES_PER_EU))) void rt_aov_kernel(const SceneDev S, const FrameDev F,
+    is_clustered(WAVE) ? RT_WAVES_PER_EU_BIG : RT_WAVES_PER_EU))) void rt_aov_kernel(const SceneDev S, const FrameDev F,
                                                                               float* __restrict__ out_t,
                                                                               int* __restrict__ out_id,
                                                                               float* __restrict__ out_n)
 {
-    static_assert(WAVE == 0 || WAVE == 1 || WAVE == 9 || WAVE == 2 || WAVE == 10, "rt_aov_kernel variants");
+    static_assert((WAVE & ~(kCullMask | kCamBuf)) == 0 && cull_mode(WAVE) <= kCullClustered &&
+                      (culls_by_wave(WAVE) || !has_cam_buf(WAVE)),
+                  "rt_aov_kernel variants");
     int bx, by;
     if (!tile_of_block<WAVE>(F, bx, by)) return;
     const int lane = threadIdx.x & 63;
@@ -77,12 +81,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
     Counters cnt;  // the hit routines' tallies: dead here
     float t;
     int idx;
-    if constexpr (WAVE == 0) {
+    if constexpr (cull_mode(WAVE) == kCullNone) {
         idx = closest_hit<false>(S, O, D, t, cnt);
     } else {
         // the camera-buffer tile, as in trace_tile
         int tile = -1;
-        if ((WAVE & 8) && S.cb_tiles_x > 0 && (py0 & 7) == 0) {
+        if (has_cam_buf(WAVE) && S.cb_tiles_x > 0 && (py0 & 7) == 0) {
             tile = (py0 >> 3) * S.cb_tiles_x + bx;
             if (S.cb_flag[tile]) tile = -1;
         }

@@ -571,7 +571,7 @@ static bool frame_ok(const rt_frame* f)
 static bool cb_async_pays(const rt_ctx* c, const rt_frame* f)
 {
     if (c->opt_camera_buffer == 2) return true;
-    return c->n_tri > kClusterMinTriangles && (double)f->width * frame_rows(f) >= 4e6;
+    return c->n_tri > kClusterMinTriangles && !small_frame((double)f->width * frame_rows(f));
 }
 
 #endif  // RT_AMD_RT_CAMHOST_H

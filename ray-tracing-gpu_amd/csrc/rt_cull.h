@@ -8,7 +8,9 @@
 
 #include <cstring>
 
+#include "rt_dims.h"
 #include "rt_primitives.h"
+#include "rt_variant.h"
 
 #pragma clang fp contract(off)
 
@@ -106,18 +108,8 @@ __device__ __forceinline__ bool edges_open(const WaveCone& wc, const float4* e, 
     return edge_open(wc, e[0], ang) & edge_open(wc, e[1], ang) & edge_open(wc, e[2], ang);
 }
 
-// Per-wave LDS windows (dynamic LDS, one per wave): the light-buffer walk's
-// staged entries (rt_shade.h lb_walk_lds: kLbLdsCap entries of a, b,
-// c per wave) and the camera-list walk's staged records (a, b:
-// kLbLdsCap / 2 records of 64 B per wave).  The two walks never overlap in a
-// wave.
-#ifndef RT_LB_LDS_CAP
-#define RT_LB_LDS_CAP 64
-#endif
-constexpr int kLbLdsCap = RT_LB_LDS_CAP;  // entries per wave window
-// The wave's window in the launch's dynamic LDS (kLdsWaveBytes per wave of
-// the workgroup, trace_dims on the host): a[cap], b[cap] float4, c[cap] float2.
-constexpr size_t kLdsWaveBytes = (size_t)kLbLdsCap * 40;
+// The wave's window in the launch's dynamic LDS (rt_dims.h kLbLdsCap,
+// kLdsWaveBytes): a[cap], b[cap] float4, c[cap] float2.
 struct LdsWin {
     float4* a;
     float4* b;
@@ -398,7 +390,7 @@ __device__ __forceinline__ int closest_hit_camera_list(const SceneDev& S, int ti
     return bi;
 }
 
-// Camera records in the launch (tiny scenes, WAVE bit 32).  For a scene of
+// Camera records in the launch (tiny scenes, kTiny of rt_variant.h).  For a scene of
 // at most kTinyMax triangles the host computes, per camera, every triangle's
 // camera cone and edge records (cone_record, in double), its tricam record
 // (the values Triangle.cpp:139-160 computes for a ray from the camera) and
@@ -413,9 +405,9 @@ __device__ __forceinline__ int closest_hit_camera_list(const SceneDev& S, int ti
 // tile_wbound).  That is the camera buffer's test with the tile's measured
 // cone replaced by a provably wider one, so the kept set holds every
 // triangle any ray of the tile can be reported hitting.  A camera's first two
-// frames on a stream (WAVE bit 64) compute each tile's mask in the trace
+// frames on a stream (kMaskCompute) compute each tile's mask in the trace
 // kernel itself — lane j tests triangle j, one ballot —, the second also
-// stores it (bit 128, rt_camhost.h tiny_masks); its later frames on that
+// stores it (kMaskStore, rt_camhost.h tiny_masks); its later frames on that
 // stream read it (one scalar load).
 // The stored word: bits 0-19 the mask; bits 20 + 2 li and 21 + 2 li light
 // li's class for the tile, li < kTinyClassLights (a later light has none):
@@ -660,18 +652,18 @@ __device__ __forceinline__ int closest_hit_camera_tiny(const SceneDev& S, const 
 }
 
 // Primary rays: wave-culled when the whole wave is here, else per lane.
-// WAVE: 0 per lane only, 1 wave-level culling, 2 wave-level two-level
-// (clustered) culling.
-// tile >= 0: the wave is that camera-buffer tile (WAVE bit 8).
+// WAVE (rt_variant.h): kCullNone per lane only, kCullWave wave-level
+// culling, kCullClustered wave-level two-level (clustered) culling.
+// tile >= 0: the wave is that camera-buffer tile (kCamBuf).
 template <int WAVE>
 __device__ __forceinline__ int closest_hit_primary(const SceneDev& S, const Vec3 O, const Vec3 D, float& t,
                                                    Counters& cnt, int tile = -1)
 {
-    if ((WAVE & 8) && tile >= 0 && wave_full())
-        return closest_hit_camera_list<(WAVE & 2) != 0>(S, tile, O, D, t, cnt);
-    if ((WAVE & 3) > 0 && wave_full()) {
+    if (has_cam_buf(WAVE) && tile >= 0 && wave_full())
+        return closest_hit_camera_list<is_clustered(WAVE)>(S, tile, O, D, t, cnt);
+    if (culls_by_wave(WAVE) && wave_full()) {
         const WaveCone wc = wave_cone(D, true);
-        if (wc.ok) return closest_hit_camera_wave<(WAVE & 3) == 2>(S, wc, O, D, t, cnt);
+        if (wc.ok) return closest_hit_camera_wave<is_clustered(WAVE)>(S, wc, O, D, t, cnt);
     }
     return S.use_tricam ? closest_hit_camera(S, O, D, t, cnt) : closest_hit<true>(S, O, D, t, cnt);
 }

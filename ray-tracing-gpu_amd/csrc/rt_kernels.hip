@@ -46,7 +46,7 @@
 #include "rt_bvh.h"
 #include "rt_wavefront.h"
 #include "rt_resolve.h"
-#include "rt_scenehost.h"  // scene_host_build, lb_plan; kClusterMinTriangles, RT_BVH_MIN_TRIANGLES
+#include "rt_scenehost.h"  // scene_host_build, lb_plan; RT_BVH_MIN_TRIANGLES
 
 #pragma clang fp contract(off)
 
@@ -67,7 +67,7 @@ struct Refr {
     float rior, energy;
 };
 
-// WAVE bit 512 (MAXD 0, the wavefront's level 0, rt_wavefront.h): a hit
+// kWf0 (MAXD 0, the wavefront's level 0, rt_wavefront.h): a hit
 // that spawns children writes a node record and its child rays instead of
 // its colour (deferred: rt_wf_fold writes the pixel).
 template <int MAXD, int LB, int WAVE>
@@ -78,7 +78,7 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
     if constexpr (MAXD == 0) {
         float t;
         RT_MARK(cnt, 0);
-        const int idx = closest_hit_primary<(WAVE & 107)>(S, O, D, t, cnt, tile);
+        const int idx = closest_hit_primary<camera_ray_bits(WAVE)>(S, O, D, t, cnt, tile);
         RT_MARK(cnt, 1);
         // Lanes that miss (or lie outside the frame) stay in step through the
         // shading so the wave stays whole for wave-level shadow culling.
@@ -99,10 +99,10 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
         }
         const Vec3 P = O + t * D;
         const Color c = shade_local<LB, WAVE>(S, m, P, N, D, cnt, hit & live);
-        if constexpr ((WAVE & 512) != 0)
+        if constexpr (is_wf0(WAVE))
             deferred = wf_children(F, 0, hit & live, m, P, N, D, 1.0f, 1.0f, c, pix, chunk, sidx);
         return hit ? c : bg;
-    } else if constexpr ((WAVE & 1024) != 0) {
+    } else if constexpr (is_chain(WAVE)) {
         // Reflect-only scenes (no Kt can pass the gate: the host's kt_max <= 0
         // with min_energy >= 0): every node has at most one child, the
         // reflected ray, and its colour is acc + C_child * Kr (Scene.cpp:1787).
@@ -123,8 +123,8 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
             float t;
             int idx;
             if (lv == 0)
-                idx = closest_hit_primary<(WAVE & 107)>(S, O, D, t, cnt, tile);
-            else if constexpr ((WAVE & 256) != 0)  // bounce rays through the BVH (rt_bvh.h)
+                idx = closest_hit_primary<camera_ray_bits(WAVE)>(S, O, D, t, cnt, tile);
+            else if constexpr (has_bvh(WAVE))  // bounce rays through the BVH (rt_bvh.h)
                 idx = closest_hit_bvh(S, O, D, t, cnt);
             else
                 idx = closest_hit<false>(S, O, D, t, cnt);
@@ -175,8 +175,8 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
                 float t;
                 int idx;
                 if (camera_ray)
-                    idx = closest_hit_primary<(WAVE & 107)>(S, O, D, t, cnt, tile);
-                else if constexpr ((WAVE & 256) != 0)  // bounce rays through the BVH (rt_bvh.h)
+                    idx = closest_hit_primary<camera_ray_bits(WAVE)>(S, O, D, t, cnt, tile);
+                else if constexpr (has_bvh(WAVE))  // bounce rays through the BVH (rt_bvh.h)
                     idx = closest_hit_bvh(S, O, D, t, cnt);
                 else
                     idx = closest_hit<false>(S, O, D, t, cnt);
@@ -265,7 +265,7 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
 
 // Occupancy floor (waves per SIMD) for the depth-0 kernels: 7 (<= 72
 // VGPRs, no spills) — C2 -4% against the unconstrained 5 waves, 6 waves
-// +1-3% and 8 waves +40% (spills) at C2/C4.  The big-list kernels (WAVE 14:
+// +1-3% and 8 waves +40% (spills) at C2/C4.  The big-list kernels (is_big_list_cam:
 // C3, C5) ran at 8 in round 1 (-3/-4% against 7) while spilling 9-10 VGPRs
 // (44 B/lane of scratch: 1.4 GB of writes per C5 frame, tools/calib); with
 // the LDS walks and an unpipelined global walk they fit 72 VGPRs with no
@@ -277,7 +277,7 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
 #ifndef RT_WAVES_PER_EU_BIG
 #define RT_WAVES_PER_EU_BIG 7
 #endif
-// The launch-camera kernel that computes its tile masks (WAVE bit 64) is
+// The launch-camera kernel that computes its tile masks (kMaskCompute) is
 // held to 64 VGPRs, 8 waves/SIMD (A/B, moving C2 camera: -2.3% against 7;
 // the mask-reading kernel fits 58 VGPRs anyway, and asked for 8 measured
 // +2.4% static).  Its mask planes are loaded at the top of the kernel (A/B:
@@ -288,8 +288,8 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
 constexpr int waves_per_eu(int maxd, int wave)
 {
     return maxd != 0 ? 1
-                     : ((wave & 64) ? RT_WAVES_PER_EU_TINY
-                                    : ((wave & 15) == 14 ? RT_WAVES_PER_EU_BIG : RT_WAVES_PER_EU));
+                     : (computes_mask(wave) ? RT_WAVES_PER_EU_TINY
+                                            : (is_big_list_cam(wave) ? RT_WAVES_PER_EU_BIG : RT_WAVES_PER_EU));
 }
 // One 8 x 8 tile (the body of both trace kernels below).
 // COUNT: also tally the exact tests executed (the RT_FLAG_STATS launch); in
@@ -336,7 +336,7 @@ __device__ __forceinline__ void trace_tile(const SceneDev& S, const FrameDev& F,
         // full frame (the lists and boxes hold for its lanes' clamped pixels,
         // a superset of the wave's)
         int tile = -1;
-        if ((WAVE & 8) && S.cb_tiles_x > 0 && (py0 & 7) == 0) {
+        if (has_cam_buf(WAVE) && S.cb_tiles_x > 0 && (py0 & 7) == 0) {
             tile = (py0 >> 3) * S.cb_tiles_x + tile_x;
             if (S.cb_flag[tile]) tile = -1;
         }
@@ -359,7 +359,7 @@ __device__ __forceinline__ void trace_tile(const SceneDev& S, const FrameDev& F,
             // line) for -0.5%.
             if (rgba) {
                 const unsigned px8 = unorm8(c.r) | (unorm8(c.g) << 8) | (unorm8(c.b) << 16) | 0xFF000000u;
-                if constexpr (!(WAVE & 2)) __builtin_nontemporal_store(px8, rgba + o);
+                if constexpr (!is_clustered(WAVE)) __builtin_nontemporal_store(px8, rgba + o);
                 else rgba[o] = px8;
             }
         }
@@ -397,8 +397,8 @@ __device__ __forceinline__ bool tile_of_block(const FrameDev& F, int& bx, int& b
 {
     bx = (int)blockIdx.x;
     by = (int)blockIdx.y;
-    constexpr unsigned K = (WAVE & 2) ? RT_XCD_CHUNK_BIG : RT_XCD_CHUNK_SMALL;
-    if constexpr ((WAVE & 2) != 0) {
+    constexpr unsigned K = is_clustered(WAVE) ? RT_XCD_CHUNK_BIG : RT_XCD_CHUNK_SMALL;
+    if constexpr (is_clustered(WAVE)) {
         const unsigned w = blockIdx.y * gridDim.x + blockIdx.x;
         const unsigned x = w % kXcds, i = w / kXcds;
         if (F.xcd_mode == 2) {
@@ -445,7 +445,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
 // wave-uniform load from the scalar cache).
 #define RT_PIN4(a, b, c, d) asm("" : "+s"(a), "+s"(b), "+s"(c), "+s"(d))
 
-// Tiny scenes (WAVE bit 32): one 8 x 8 tile of a depth-0 frame whose
+// Tiny scenes (kTiny): one 8 x 8 tile of a depth-0 frame whose
 // wave-uniform inputs all come with the launch (rt_cull.h TinyLaunch, one
 // by-value argument read from the kernel-argument segment by scalar loads).
 // trace_tile's frame geometry, radiance<0>'s hit and store, with the
@@ -453,12 +453,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
 // (issued straight behind it, in flight under the ray set-up), one per kept
 // triangle, the hit's normal and material, and per light its record, its
 // cell's offsets and one per entry.
-// WAVE bit 64: the wave computes the tile's mask; bit 128: and stores it.
+// kMaskCompute: the wave computes the tile's mask; kMaskStore: and stores it.
 template <int MAXD, int LB, int WAVE, bool COUNT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu(MAXD, WAVE)))) void rt_trace_tiny(
     const TinyLaunch L)
 {
-    static_assert(MAXD == 0 && LB == 1 && (WAVE & 37) == 37, "the launch-camera kernels are depth-0, light-buffer");
+    static_assert(MAXD == 0 && LB == 1 && (WAVE & kTinyRead) == kTinyRead,
+                  "the launch-camera kernels are depth-0, light-buffer");
     const TinyHead& H = L.h;
     // ---- the header's camera / frame / mask / plane part, under one wait
     FrameDev F{};
@@ -514,10 +515,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     // the full frame (the masks hold for its lanes' clamped pixels)
     const int tile = (py0 & 7) == 0 ? (py0 >> 3) * tiles_x + bx : -1;
     const bool tiled = masked && tile >= 0;
-    if constexpr ((WAVE & 64) == 0)
+    if constexpr (!computes_mask(WAVE))
         if (tiled) tm = mask[tile];  // wave-uniform (scalar) load, waited for at the triangles
     TinyLane tl;
-    if constexpr ((WAVE & 64) != 0) tl = tiny_lane_load(tn, L.rec);  // the mask's records, in flight under the set-up
+    if constexpr (computes_mask(WAVE)) tl = tiny_lane_load(tn, L.rec);  // the mask's records, in flight under set-up
     const int py = py0 + (lane >> 3);
     const bool valid = px < F.width && py < rend;
 
@@ -533,7 +534,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     const Vec3 O = make3(F.cam[0], F.cam[1], F.cam[2]);
     cnt.primary = valid ? 1u : 0u;
     unsigned tmask = 0;
-    if constexpr ((WAVE & 64) != 0) {
+    if constexpr (computes_mask(WAVE)) {
         tmask = tiny_tile_mask(tn, tl, D);
         if (tiled) tm = tmask;
     }
@@ -555,9 +556,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     // stored word, gathered by the storing frame, neither by a camera's first
     // frame.  A counted render runs every pass (its counters are the general
     // kernels'); a wave without a tile has tm_all's zero bits there.
-    constexpr int CLS = (WAVE & 128) != 0 ? 2 : ((WAVE & 64) == 0 && !COUNT) ? 1 : 0;
+    constexpr int CLS = stores_mask(WAVE) ? 2 : (!computes_mask(WAVE) && !COUNT) ? 1 : 0;
     unsigned cls = 0;
-    if constexpr ((WAVE & 64) == 0) {
+    if constexpr (!computes_mask(WAVE)) {
         if constexpr (CLS == 1) cls = tm >> kTinyClassShift;
         tm &= (1u << kTinyClassShift) - 1u;
     }
@@ -597,20 +598,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
         if (rgba)
             __builtin_nontemporal_store(unorm8(c.r) | (unorm8(c.g) << 8) | (unorm8(c.b) << 16) | 0xFF000000u, rgba + o);
     }
-    // the tile's mask for its camera's later frames on this stream (WAVE
-    // bit 128), stored last: at the top of the kernel the store's
+    // the tile's mask for its camera's later frames on this stream
+    // (kMaskStore), stored last: at the top of the kernel the store's
     // completion held up the loads behind it (A/B: C2 -2.8%, C4 -2.5%).
     // Above the mask's 20 bits, the light classes the shading gathered (0
     // where the tile was not shaded).
-    if constexpr ((WAVE & 128) != 0)
+    if constexpr (stores_mask(WAVE))
         if (lane == 0 && tiled) mask[tile] = tmask | cls << kTinyClassShift;
     tile_prof_flush(cnt);
     if (COUNT && (H.flags & RT_FLAG_STATS)) tile_tally(cnt, H.stats, true);  // (every lane runs)
 }
-
-// Compiled bounce-stack capacities.  The host picks the smallest one that
-// covers the bounce depth the scene can actually reach.
-#define RT_STACK_DEPTHS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(8) X(12) X(16) X(20) X(32)
 
 // Self-test of the wave primitives the culling relies on (rt_debug_selftest):
 // wave_min / wave_max / wave_sum_u64 against plain loops over the same lane
@@ -1907,86 +1904,39 @@ static int reachable_depth(const rt_ctx* c, const rt_frame* f)
     return levels;
 }
 
-typedef void (*kernel_fn)(const SceneDev, const FrameDev, unsigned*, float*, StatsDev*);
-
-// Kernel variants (tools/ab_variants.py, MI355X).  Without bounces and with
-// triangles: wave-level culling (two-level above kClusterMinTriangles),
-// RT_WAVE_LB lights per shadow pass (1: with the camera buffer and the union
-// pre-test, C2 -5.3% and C4 -6.9% against 2; 3 is 50% slower).  Without
-// triangles nothing is culled: light batches of 3.  Bounce kernels:
-// per-lane culling, one light per pass (LB 3 regressed scene7 by 4%).
-#ifndef RT_WAVE_LB
-#define RT_WAVE_LB 1
-#endif
-// The trace kernel of a frame: its function, bounce-stack capacity (-1:
-// none compiled), lights per shadow pass, dynamic LDS per workgroup, and its
-// name (rt_stats.kernel).
+// The kernel of a frame (pick_kernel): its function (nullptr: none compiled),
+// its variant — bounce-stack capacity, lights per shadow pass, flags —, its
+// dynamic LDS per workgroup, and its name (rt_stats.kernel).
 struct KernelPick {
-    kernel_fn k = nullptr;
-    int cap = 0, lb = 1, wave = 0;
+    const void* k = nullptr;
+    Variant v;
     unsigned lds = 0;
-    char name[48] = {};
+    const KernelName* name = nullptr;
 };
-template <int MAXD, int LB, int WAVE, bool COUNT>
-static KernelPick kpick(unsigned lds)
+// One compiled variant in a kernel table: rt_variant.h's lists are expanded
+// into these tables and nowhere else.  Which kernel counts (COUNT, the
+// RT_FLAG_STATS launch) differs by table, each keeping the order its kernels
+// have in the code object:
+//   kTinyKernels             k[count]: k[0] timed, k[1] counted;
+//   kWfShadeKernels<STRAG>   k[!count]: k[0] counted, k[1] timed;
+//   kWf0Kernels<COUNT>, kFrameKernels<COUNT>   COUNT is the table's parameter, k[0];
+//   kAovKernels              k[0] (AOV frames take no RT_FLAG_STATS).
+// A row looked up for a variant that select_variant returned exists, except
+// for a depth above the compiled stacks (pick_kernel):
+// tools/variant/variant_check.cpp walks the facts the host can form and
+// checks every selection against the lists.
+template <int N>
+struct KernelRow {
+    Variant v;
+    const void* k[N];
+    KernelName name;
+};
+template <int N, size_t ROWS>
+static const KernelRow<N>* find_row(const KernelRow<N> (&table)[ROWS], const Variant& v)
 {
-    KernelPick p;
-    p.k = (kernel_fn)&rt_trace_kernel<MAXD, LB, WAVE, COUNT>;
-    p.cap = MAXD;
-    p.lb = LB;
-    p.wave = WAVE;
-    p.lds = lds;
-    std::snprintf(p.name, sizeof p.name, "rt_trace_kernel<%d,%d,%d>", MAXD, LB, WAVE);
-    return p;
-}
-// bvh: bounce rays through the BVH (depth > 0, the scene's BVH built, light
-// buffer on): WAVE bit 256 with the depth-0 kernels' camera and shadow paths
-// (camera buffer bit 8 — a no-op when S.cb_tiles_x is 0 —, light buffer bit
-// 4, wave culling 1 or clustered 2); its waves carry the traversal stacks in
-// LDS after the staging window.
-// chain: no refracted ray can pass its gate (reflect-only scenes): the
-// bounce kernels keep the chain in registers (WAVE bit 1024).
-// small: a frame under 4 Mpx of output rows — the big-list kernel walks the
-// light buffer's per-lane lists two entries per round (WAVE bit 2048,
-// rt_shade.h lb_slot: its 8 x 8 tiles see more cells there than the staged
-// walk takes; C3 -6%, and no gain at C5 for the registers it holds,
-// profiles/r06/lbwalk/).
-template <bool COUNT>
-static KernelPick pick_kernel(int depth, int n_tri, int n_lights, bool lbuf, bool cbuf, int bvh_depth = 0,
-                              bool chain = false, bool small = false)
-{
-    const bool bvh = bvh_depth > 0;
-    const unsigned win = (unsigned)kLdsWaveBytes;
-    if (depth == 0 && n_tri > 0 && lbuf) {  // light-buffer shadows, one light per pass
-        if (n_tri > kClusterMinTriangles) {
-            if (small) return cbuf ? kpick<0, 1, 2062, COUNT>(win) : kpick<0, 1, 2054, COUNT>(win);
-            return cbuf ? kpick<0, 1, 14, COUNT>(win) : kpick<0, 1, 6, COUNT>(win);
-        }
-        return cbuf ? kpick<0, 1, 13, COUNT>(0) : kpick<0, 1, 5, COUNT>(0);
-    }
-    if (depth == 0 && n_tri > kClusterMinTriangles)
-        return cbuf ? kpick<0, RT_WAVE_LB, 10, COUNT>(win) : kpick<0, RT_WAVE_LB, 2, COUNT>(win);
-    if (depth == 0 && n_tri > 0)
-        return cbuf ? kpick<0, RT_WAVE_LB, 9, COUNT>(0) : kpick<0, RT_WAVE_LB, 1, COUNT>(0);
-    if (depth == 0 && n_lights > 1) return kpick<0, 3, 0, COUNT>(0);
-    const unsigned bl = (unsigned)(kLdsWaveBytes + (size_t)bvh_depth * 64 * sizeof(int));
-    if (bvh && lbuf && n_tri > 0) {
-#define RT_PICK_BVH(N)                                                                                     \
-    if (depth <= N) {                                                                                      \
-        if (chain)                                                                                         \
-            return n_tri > kClusterMinTriangles ? kpick<N, 1, 1294, COUNT>(bl) : kpick<N, 1, 1293, COUNT>(bl); \
-        return n_tri > kClusterMinTriangles ? kpick<N, 1, 270, COUNT>(bl) : kpick<N, 1, 269, COUNT>(bl);   \
-    }
-        RT_STACK_DEPTHS(RT_PICK_BVH)
-#undef RT_PICK_BVH
-    }
-#define RT_PICK(N) \
-    if (depth <= N) return chain ? kpick<N, 1, 1024, COUNT>(0) : kpick<N, 1, 0, COUNT>(0);
-    RT_STACK_DEPTHS(RT_PICK)
-#undef RT_PICK
-    KernelPick none;
-    none.cap = -1;
-    return none;
+    for (const KernelRow<N>& r : table)
+        if (r.v == v) return &r;
+    return nullptr;
 }
 
 // Launch shape of a trace kernel over `rows` output rows: one 8 x 8 tile per
@@ -1998,20 +1948,18 @@ static void trace_dims(int width, int rows, dim3& grid, dim3& block)
     block = dim3(64);
 }
 
-// The launch-camera kernel (tiny scenes: camera buffer replaced by the
-// launch's records, light-buffer shadows, one light per pass); SELF: the
-// camera's first frame on the stream, which computes and stores the masks.
-// By tile-mask mode (tiny_masks): its WAVE value and kernels, k[COUNT].
-struct TinyKernel {
-    int wave;
-    const void* k[2];
-};
-#define RT_TINY(W) {W, {(const void*)&rt_trace_tiny<0, 1, W, false>, (const void*)&rt_trace_tiny<0, 1, W, true>}}
-static const TinyKernel kTinyKernels[3] = {RT_TINY(37), RT_TINY(101), RT_TINY(229)};
-#undef RT_TINY
+// The launch-camera kernels (tiny scenes: camera buffer replaced by the
+// launch's records, light-buffer shadows, one light per pass), one per
+// tile-mask mode (tiny_masks); k[COUNT].
+#define RT_V(M, L, F)                                                                                           \
+    {{M, L, F},                                                                                                 \
+     {(const void*)&rt_trace_tiny<M, L, F, false>, (const void*)&rt_trace_tiny<M, L, F, true>},                 \
+     kernel_name("rt_trace_tiny", M, L, F)},
+static const KernelRow<2> kTinyKernels[] = {RT_TINY_VARIANTS};
+#undef RT_V
 
 // The launch grid over `rows` output rows and the frame's tile-dealing fields
-// (tile_of_block); big: a big-list kernel (WAVE bit 2), whose RT_OPT_XCD_DEAL
+// (tile_of_block); big: a big-list kernel (is_clustered), whose RT_OPT_XCD_DEAL
 // modes other than 1 launch padded grids.
 static void trace_grid(const rt_ctx* c, bool big, FrameDev& F, int width, int rows, dim3& grid, dim3& block)
 {
@@ -2038,26 +1986,24 @@ static void trace_grid(const rt_ctx* c, bool big, FrameDev& F, int width, int ro
     }
 }
 
-// One trace launch over `rows` output rows (T: the launch-camera kernel with
-// its records, else kernel k).
-static int launch_trace(rt_ctx* c, const KernelPick& kp, const TinyCam* T, bool count, SceneDev& S, FrameDev& F,
-                        int width, int rows, unsigned* oa, float* ob, StatsDev* stats, hipStream_t st, int mode = 0)
+// One trace launch of kernel kp over `rows` output rows (T: its records, when
+// it is a launch-camera kernel).
+static int launch_trace(rt_ctx* c, const KernelPick& kp, const TinyCam* T, SceneDev& S, FrameDev& F, int width,
+                        int rows, unsigned* oa, float* ob, StatsDev* stats, hipStream_t st)
 {
     dim3 grid, block;
-    trace_grid(c, !T && (kp.wave & 2), F, width, rows, grid, block);
+    trace_grid(c, is_clustered(kp.v.flags), F, width, rows, grid, block);
+    void* args[] = {&S, &F, &oa, &ob, &stats};
+    TinyLaunch Lr;
     if (T) {
         // the launch record (rt_cull.h TinyLaunch): the frame's, the scene's
-        // and the camera records' wave-uniform values, one argument
-        TinyLaunch Lr;
+        // and the camera records' wave-uniform values, the one argument
         tiny_head_fill(Lr.h, F, S, *T, c->h_plane.data(),
                        c->d_lrec + (c->opt_lb_region ? 0 : kLightRec * S.n_lights), oa, ob, stats);
         std::memcpy(Lr.rec, T->rec, sizeof Lr.rec);
-        void* args[] = {&Lr};
-        HIP_TRY(c, hipLaunchKernel(kTinyKernels[mode].k[count], grid, block, args, 0, st));
-        return RT_OK;
+        args[0] = &Lr;
     }
-    void* args[] = {&S, &F, &oa, &ob, &stats};
-    HIP_TRY(c, hipLaunchKernel((const void*)kp.k, grid, block, args, kp.lds, st));
+    HIP_TRY(c, hipLaunchKernel(kp.k, grid, block, args, kp.lds, st));
     return RT_OK;
 }
 
@@ -2462,19 +2408,15 @@ static int wf_ensure(rt_ctx* c, const rt_frame* f, int rows, int levels, bool ca
     return RT_OK;
 }
 
-// Level 0 of a wavefront frame: the depth-0 kernel with WAVE bit 512.
-template <bool COUNT>
-static KernelPick pick_wf0(int n_tri, bool cbuf, bool small = false)
-{
-    const unsigned win = (unsigned)kLdsWaveBytes;
-    if (n_tri > kClusterMinTriangles && small)  // (the two-entry light-buffer walk, pick_kernel)
-        return cbuf ? kpick<0, 1, 2574, COUNT>(win) : kpick<0, 1, 2566, COUNT>(win);
-    if (n_tri > kClusterMinTriangles)
-        return cbuf ? kpick<0, 1, 526, COUNT>(win) : kpick<0, 1, 518, COUNT>(win);
-    return cbuf ? kpick<0, 1, 525, COUNT>(0) : kpick<0, 1, 517, COUNT>(0);
-}
-
-static bool W_px_small(const rt_ctx* c) { return (double)c->wf.px < 4e6; }
+// The shading kernels of the wavefront's bounce levels; k[0] counts
+// (RT_FLAG_STATS), k[1] is the timed one.  STRAG: the stragglers' launch.
+#define RT_V(M, L, F)                                                                                        \
+    {{M, L, F},                                                                                              \
+     {(const void*)&rt_wf_shade<F, true, STRAG>, (const void*)&rt_wf_shade<F, false, STRAG>},                \
+     kernel_name("rt_wf_shade", F)},
+template <bool STRAG>
+static const KernelRow<2> kWfShadeKernels[] = {RT_WF_SHADE_VARIANTS};
+#undef RT_V
 
 // The bounce levels and folds of a wavefront frame, after level 0 on st:
 // per level a trace launch (the BVH walk; LDS = its stack) and a shade
@@ -2482,22 +2424,19 @@ static bool W_px_small(const rt_ctx* c) { return (double)c->wf.px < 4e6; }
 static int wf_levels(rt_ctx* c, const SceneDev& S, const FrameDev& F, int levels, bool count, unsigned* rgba,
                      float* rgbf, StatsDev* stats, hipStream_t st)
 {
-    const bool big = c->n_tri > kClusterMinTriangles;
     const void* kt = count ? (const void*)&rt_wf_trace<true> : (const void*)&rt_wf_trace<false>;
     const void* kg = count ? (const void*)&rt_wf_straggle<true> : (const void*)&rt_wf_straggle<false>;
-    // (frames under 4 Mpx: the two-entry light-buffer walk, pick_kernel)
-    const bool small = c->opt_lb_unroll && W_px_small(c);
-    const void* ks = big ? (small ? (count ? (const void*)&rt_wf_shade<2054, true> : (const void*)&rt_wf_shade<2054, false>)
-                                  : (count ? (const void*)&rt_wf_shade<6, true> : (const void*)&rt_wf_shade<6, false>))
-                         : (count ? (const void*)&rt_wf_shade<5, true> : (const void*)&rt_wf_shade<5, false>);
+    Facts fa;
+    fa.wf_shade = true;
+    fa.n_tri = c->n_tri;
+    fa.small = c->opt_lb_unroll && small_frame((double)c->wf.px);
+    const Variant vs = select_variant(fa);
+    const void* ks = find_row(kWfShadeKernels<false>, vs)->k[!count];  // (the row exists: KernelRow)
     // (RT_OPT_WF_OVERLAP: the stragglers' walks and shading on a second
     // stream, beside the level's main shade launch)
-    const void* ks2 =
-        big ? (small ? (count ? (const void*)&rt_wf_shade<2054, true, true> : (const void*)&rt_wf_shade<2054, false, true>)
-                     : (count ? (const void*)&rt_wf_shade<6, true, true> : (const void*)&rt_wf_shade<6, false, true>))
-            : (count ? (const void*)&rt_wf_shade<5, true, true> : (const void*)&rt_wf_shade<5, false, true>);
+    const void* ks2 = find_row(kWfShadeKernels<true>, vs)->k[!count];
     const unsigned lds_t = (unsigned)((size_t)c->bvh_depth * 64 * sizeof(int));
-    const unsigned lds_s = big ? (unsigned)kLdsWaveBytes : 0u;
+    const unsigned lds_s = lds_bytes(vs.flags, 0);
     rt_ctx::WfBuf& W = c->wf;
     const bool ovl = c->opt_wf_overlap;
     if (ovl) {
@@ -2673,6 +2612,58 @@ static int stream_capturing(rt_ctx* c, hipStream_t st, bool* capturing)
     return RT_OK;
 }
 
+// ---- the trace kernels (rt_variant.h: what a variant is, which one a frame
+// takes, and the lists of the compiled ones)
+// COUNT: the kernels that also tally the tests executed (the RT_FLAG_STATS
+// launch).  It is the tables' parameter, and level 0 of the wavefront has a
+// table of its own, because the code object holds its kernels in the order
+// in which they are first named here: level 0 counted, timed, then the
+// frames' counted, timed.
+#define RT_V(M, L, F) \
+    {{M, L, F}, {(const void*)&rt_trace_kernel<M, L, F, COUNT>}, kernel_name("rt_trace_kernel", M, L, F)},
+template <bool COUNT>
+static const KernelRow<1> kWf0Kernels[] = {RT_TRACE_WF0_VARIANTS};
+template <bool COUNT>
+static const KernelRow<1> kFrameKernels[] = {RT_TRACE_FRAME_VARIANTS};
+#undef RT_V
+
+// The facts of frame f that every colour path shares; the caller adds its own
+// (small, wf0, tiny).
+static Facts frame_facts(const rt_ctx* c, const rt_frame* f, int depth, bool lbuf, bool cbuf, bool bvh)
+{
+    Facts a;
+    a.depth = depth;
+    a.n_tri = c->n_tri;
+    a.n_lights = c->n_lights;
+    a.lbuf = lbuf;
+    a.cbuf = cbuf;
+    a.bvh_depth = bvh ? c->bvh_depth : 0;
+    a.chain = reflect_chain(c, f);
+    return a;
+}
+
+// The colour kernel of a frame: the selected variant's row (k == nullptr:
+// the reachable depth exceeds the compiled stacks).
+static KernelPick pick_kernel(const Facts& a, bool count)
+{
+    KernelPick p;
+    p.v = select_variant(a);
+    if (is_tiny(p.v.flags)) {
+        const KernelRow<2>* r = find_row(kTinyKernels, p.v);  // (the row exists: KernelRow)
+        p.k = r->k[count];
+        p.name = &r->name;
+        return p;
+    }
+    const KernelRow<1>* r = is_wf0(p.v.flags)
+                                ? (count ? find_row(kWf0Kernels<true>, p.v) : find_row(kWf0Kernels<false>, p.v))
+                                : (count ? find_row(kFrameKernels<true>, p.v) : find_row(kFrameKernels<false>, p.v));
+    if (!r) return p;
+    p.k = r->k[0];
+    p.name = &r->name;
+    p.lds = lds_bytes(p.v.flags, a.bvh_depth);
+    return p;
+}
+
 // ---- a colour frame: plan_frame decides, launch enqueues what was decided.
 // The plan of one frame: its kernel and that kernel's arguments, and its
 // packed rows as chunks [r0, r0 + step) — step == rows: one chunk
@@ -2754,13 +2745,11 @@ static int plan_frame(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync_pa
         if (!B.ev) HIP_TRY(c, hipEventCreateWithFlags(&B.ev, hipEventDisableTiming));
     }
     const bool count = (f->flags & RT_FLAG_STATS) != 0;
-    const bool small = (double)f->width * rows < 4e6 && c->opt_lb_unroll;
-    P.kp = wf ? (count ? pick_wf0<true>(c->n_tri, cbuf, small) : pick_wf0<false>(c->n_tri, cbuf, small))
-              : (count ? pick_kernel<true>(depth, c->n_tri, c->n_lights, lbuf, cbuf, bvh ? c->bvh_depth : 0,
-                                           reflect_chain(c, f), small)
-                       : pick_kernel<false>(depth, c->n_tri, c->n_lights, lbuf, cbuf, bvh ? c->bvh_depth : 0,
-                                            reflect_chain(c, f), small));
-    const KernelPick& kp = P.kp;
+    Facts fa = frame_facts(c, f, depth, lbuf, cbuf, bvh);
+    fa.small = small_frame((double)f->width * rows) && c->opt_lb_unroll;
+    fa.wf0 = wf;
+    fa.tiny = P.tiny ? P.tmode : -1;
+    const KernelPick& kp = P.kp = pick_kernel(fa, count);
     if (!kp.k) {
         c->err = "reachable bounce depth " + std::to_string(depth) + " exceeds the compiled stack (32)";
         return RT_E_UNSUPPORTED;
@@ -2769,14 +2758,13 @@ static int plan_frame(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync_pa
     frame_dev(f, P.F);
     if (wf) P.F.wf = c->wf.dev;
     c->last = rt_stats{};
-    c->last.stack_depth = wf ? depth : kp.cap;
-    c->last.light_batch = kp.lb;
+    c->last.stack_depth = wf ? depth : kp.v.maxd;
+    c->last.light_batch = kp.v.lb;
+    static_assert(sizeof c->last.kernel >= sizeof kp.name->s, "rt_stats.kernel holds a kernel's name");
     if (wf)
-        std::snprintf(c->last.kernel, sizeof c->last.kernel, "wavefront %s + %d levels", kp.name, depth);
-    else if (P.tiny)
-        std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_trace_tiny<0,1,%d>", kTinyKernels[P.tmode].wave);
+        std::snprintf(c->last.kernel, sizeof c->last.kernel, "wavefront %s + %d levels", kp.name->s, depth);
     else
-        std::memcpy(c->last.kernel, kp.name, sizeof kp.name);
+        std::memcpy(c->last.kernel, kp.name->s, sizeof kp.name->s);
     return RT_OK;
 }
 
@@ -2830,8 +2818,7 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
         }
         unsigned* oa = P.ss_staged ? nullptr : (rgba_dev ? rgba_dev + (size_t)r0 * f->width : nullptr);
         float* ob = P.ss_staged ? B.mem : (rgb_dev ? rgb_dev + (size_t)r0 * f->width * 3 : nullptr);
-        if (int rc = launch_trace(c, P.kp, P.tiny ? &P.T : nullptr, count, P.S, *F, f->width, r1 - r0, oa, ob, stats, st,
-                                  P.tmode))
+        if (int rc = launch_trace(c, P.kp, P.tiny ? &P.T : nullptr, P.S, *F, f->width, r1 - r0, oa, ob, stats, st))
             return rc;
         if (P.wf) {  // (one chunk)
             if (int rc = wf_levels(c, P.S, *F, P.depth, count, oa, ob, stats, st)) return rc;
@@ -3033,7 +3020,7 @@ RT_EXPORT int rt_render_sequence_async(rt_ctx* c, const rt_frame* frames, int32_
             c->err = "bad rt_frame geometry (or RT_FLAG_STATS) in a sequence";
             return RT_E_ARG;
         }
-        if (!pick_kernel<false>(reachable_depth(c, f), c->n_tri, c->n_lights, false, false).k) {
+        if (select_variant(frame_facts(c, f, reachable_depth(c, f), false, false, false)).maxd < 0) {
             c->err = "reachable bounce depth exceeds the compiled stack (32)";
             return RT_E_UNSUPPORTED;
         }
@@ -3083,8 +3070,9 @@ RT_EXPORT int rt_render_sequence_async(rt_ctx* c, const rt_frame* frames, int32_
         if (c->n_tri > 0 && !tiny) {
             if (int rc = camera_records(c, f->cam_pos, fs, cbuf, q.tricam, q.cone_cam, q.uni, q.clu_cam)) return rc;
         }
-        const KernelPick kp =
-            pick_kernel<false>(depth, c->n_tri, c->n_lights, lbuf, cbuf, bvh ? c->bvh_depth : 0, reflect_chain(c, f));
+        Facts fa = frame_facts(c, f, depth, lbuf, cbuf, bvh);
+        fa.tiny = tiny ? tmode : -1;
+        const KernelPick kp = pick_kernel(fa, false);
         SceneDev S = scene_dev(c, lbuf, false);
         S.tricam = q.tricam;
         S.cone_cam = q.cone_cam;
@@ -3102,8 +3090,7 @@ RT_EXPORT int rt_render_sequence_async(rt_ctx* c, const rt_frame* frames, int32_
         frame_dev(f, F);
         unsigned* rgba = rgba8_dev ? (unsigned*)(rgba8_dev + (size_t)i * rgba8_stride) : nullptr;
         float* rgb = rgb_dev ? (float*)((char*)rgb_dev + (size_t)i * rgb_stride) : nullptr;
-        if (int rc = launch_trace(c, kp, tiny ? &T : nullptr, false, S, F, f->width, rows, rgba, rgb, c->d_stats, fs,
-                                  tmode))
+        if (int rc = launch_trace(c, kp, tiny ? &T : nullptr, S, F, f->width, rows, rgba, rgb, c->d_stats, fs))
             return rc;
         if (tmode == 2)
             if (int rc = tiny_masks_stored(c, fs)) return rc;
@@ -3245,17 +3232,9 @@ RT_EXPORT int rt_cpu_render_ss_float(rt_ctx* c, const rt_frame* f, int32_t s, fl
 }
 
 // ---- primary-hit AOV renders (rt.h, rt_aov.h)
-typedef void (*aov_fn)(const SceneDev, const FrameDev, float*, int*, float*);
-static aov_fn aov_kernel(int wave)
-{
-    switch (wave) {
-    case 1: return &rt_aov_kernel<1>;
-    case 9: return &rt_aov_kernel<9>;
-    case 2: return &rt_aov_kernel<2>;
-    case 10: return &rt_aov_kernel<10>;
-    default: return &rt_aov_kernel<0>;
-    }
-}
+#define RT_V(M, L, F) {{M, L, F}, {(const void*)&rt_aov_kernel<F>}, kernel_name("rt_aov_kernel", F)},
+static const KernelRow<1> kAovKernels[] = {RT_AOV_VARIANTS};
+#undef RT_V
 
 // The checks every AOV entry point shares (after the backend's own).
 static int aov_check(rt_ctx* c, const rt_frame* f, const rt_aov* o)
@@ -3272,7 +3251,7 @@ static int aov_check(rt_ctx* c, const rt_frame* f, const rt_aov* o)
     return check_frame(c, f);
 }
 
-// One AOV frame into device planes on st.  The variant: WAVE 0 (no camera
+// One AOV frame into device planes on st.  The variant: kCullNone (no camera
 // state) for the scenes whose colour frames take their camera records with
 // the launch — no camera state is built or invalidated behind that kernel —
 // and for scenes without triangles; else the depth-0 colour frame's culling
@@ -3292,23 +3271,28 @@ static int launch_aov(rt_ctx* c, const rt_frame* f, const rt_aov& dev, hipStream
         if (int rc = prepare_state(c, f, st, sync_path, capturing, cb_want)) return rc;
     }
     const bool cbuf = cb_want && cb_matches(c->cb, f);
-    const int wave = wave0 ? 0 : ((c->n_tri > kClusterMinTriangles ? 2 : 1) | (cbuf ? 8 : 0));
+    Facts fa;
+    fa.aov = true;
+    fa.n_tri = c->n_tri;
+    fa.tiny = wave0 ? 0 : -1;
+    fa.cbuf = cbuf;
+    const Variant v = select_variant(fa);
+    const KernelRow<1>* const row = find_row(kAovKernels, v);  // (the row exists: KernelRow)
     SceneDev S = scene_dev(c, false, cbuf);
     FrameDev F;
     frame_dev(f, F);
     c->last = rt_stats{};
-    std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_aov_kernel<%d>", wave);
+    std::memcpy(c->last.kernel, row->name.s, sizeof row->name.s);
     c->last.primary_rays = (uint64_t)f->width * (uint64_t)ss_valid_rows(f, rows);
     if (rows == 0) return RT_OK;
     dim3 grid, block;
-    trace_grid(c, (wave & 2) != 0, F, f->width, rows, grid, block);
+    trace_grid(c, is_clustered(v.flags), F, f->width, rows, grid, block);
     float* ot = dev.t;
     int* oi = dev.id;
     float* on = dev.n;
     void* args[] = {&S, &F, &ot, &oi, &on};
     if (sync_path) HIP_TRY(c, hipEventRecord(c->ev0, st));
-    HIP_TRY(c, hipLaunchKernel((const void*)aov_kernel(wave), grid, block, args,
-                               (wave & 2) ? (unsigned)kLdsWaveBytes : 0u, st));
+    HIP_TRY(c, hipLaunchKernel(row->k[0], grid, block, args, lds_bytes(v.flags, 0), st));
     if (sync_path) HIP_TRY(c, hipEventRecord(c->ev1, st));
     if (capturing) {
         c->captured = true;

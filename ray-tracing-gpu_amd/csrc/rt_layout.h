@@ -108,7 +108,7 @@ struct SceneDev {
     // the camera (uni[0..1]) and over the opaque ones for each light
     // (uni[2 + 2l ..]); nullptr: none.
     const float4* __restrict__ uni;
-    // Camera buffer (depth-0 kernels, WAVE bit 8): per 8x8 tile of the full
+    // Camera buffer (depth-0 kernels, kCamBuf of rt_variant.h): per 8x8 tile of the full
     // frame (tile = row/8 * cb_tiles_x + col/8), the triangles the tile's
     // wave cone can reach (the camera wave test), with a key = min dmin of
     // the entry and every later one; cb_flag[tile] != 0: no list (per-wave
@@ -124,7 +124,7 @@ struct SceneDev {
     // the records' extra bytes cost more: C5 +3%, against C3 -4 to -5%).
     // Walked inline by the big-list kernel only (small lists: no gain).
     const float4* __restrict__ cb_rec;
-    // Bounce rays (WAVE bit 256, rt_bvh.h): BVH2 inner nodes (5 float4 each,
+    // Bounce rays (kBvh, rt_bvh.h): BVH2 inner nodes (5 float4 each,
     // node 0 the root) over every triangle, and the triangles in leaf order
     // (tri[]'s 48-byte layout).  nullptr: none.
     const float4* __restrict__ bvh_node;

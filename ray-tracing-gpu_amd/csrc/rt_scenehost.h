@@ -26,9 +26,6 @@
 
 namespace rt {
 
-// two-level (clustered) culling above this many triangles
-static constexpr int kClusterMinTriangles = 1024;
-
 inline bool nonneg_finite(float v) { return std::isfinite(v) && !std::signbit(v); }
 
 // Cluster order for the two-level culling: a top-down median split of the

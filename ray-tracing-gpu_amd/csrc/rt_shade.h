@@ -596,7 +596,7 @@ __device__ __forceinline__ bool lb_slot(const SceneDev& S, int slot, const Vec3 
         end = e;  // walked: skip the global walk below
     bool have = e < end;
     if constexpr (UNROLL) {
-        // The per-lane walk two entries per round (WAVE bit 2048: the
+        // The per-lane walk two entries per round (kLbPair: the
         // big-list depth-0 kernel on frames under 4 Mpx, whose 8 x 8 tiles
         // see more cells than the LDS-staged walk takes): the two loads
         // issue together, so a lit point's long list (every entry nearer
@@ -818,7 +818,7 @@ __device__ __forceinline__ Color shade_local(const SceneDev& S, const Mat& m, co
         }
         return res;
     }
-    if constexpr ((WAVE & 4) != 0) {  // light buffer: one light at a time, file order
+    if constexpr (has_light_buf(WAVE)) {  // light buffer: one light at a time, file order
         for (int li = 0; li < S.n_lights; ++li) {
             const float4 l0 = S.lights[2 * li], l1 = S.lights[2 * li + 1];
             const Vec3 Lr = make3(l0.x, l0.y, l0.z) - P;
@@ -828,7 +828,7 @@ __device__ __forceinline__ Color shade_local(const SceneDev& S, const Mat& m, co
             cnt.shadow += gate;
             bool occ = !gate;
             RT_MARK(cnt, 2);
-            shadow_opaque_lb<((WAVE) & 2) != 0, ((WAVE) & 2048) != 0>(S, li, P, L, dist, occ, cnt);
+            shadow_opaque_lb<is_clustered(WAVE), has_lb_pair(WAVE)>(S, li, P, L, dist, occ, cnt);
             RT_MARK(cnt, 7);
             if (gate) {
                 Color F{0.0f, 0.0f, 0.0f};
@@ -868,7 +868,7 @@ __device__ __forceinline__ Color shade_local(const SceneDev& S, const Mat& m, co
             occ[j] = !gate[j];
         }
         RT_MARK(cnt, 2);
-        bool use_wave = (WAVE & 3) > 0 && wave_full();
+        bool use_wave = culls_by_wave(WAVE) && wave_full();
         WaveCone wc[kLightBatch];
         float dmax[kLightBatch];
         unsigned tmask = (1u << nl) - 1u;  // lights whose triangles the wave must walk
@@ -879,7 +879,8 @@ __device__ __forceinline__ Color shade_local(const SceneDev& S, const Mat& m, co
                 dmax[j] = 0.0f;
                 if (j < nl && ((tmask >> j) & 1u)) {
                     // no lane's ray can need any triangle: skip the wave cone too
-                    if ((WAVE & 3) == 1 && S.uni && !union_reach(S.uni + 2 * (1 + lb + j), L[j], dist[j], gate[j])) {
+                    if (cull_mode(WAVE) == kCullWave && S.uni &&
+                        !union_reach(S.uni + 2 * (1 + lb + j), L[j], dist[j], gate[j])) {
                         tmask &= ~(1u << j);
                         continue;
                     }
@@ -890,7 +891,7 @@ __device__ __forceinline__ Color shade_local(const SceneDev& S, const Mat& m, co
             }
         }
         RT_MARK(cnt, 3);
-        if (use_wave) shadow_opaque_wave<kLightBatch, (WAVE & 3) == 2>(S, lb, nl, tmask, P, L, dist, occ, wc, dmax, cnt);
+        if (use_wave) shadow_opaque_wave<kLightBatch, is_clustered(WAVE)>(S, lb, nl, tmask, P, L, dist, occ, wc, dmax, cnt);
         else shadow_opaque_batch<kLightBatch>(S, lb, nl, P, L, dist, occ, cnt);
         RT_MARK(cnt, 4);
 #pragma unroll

@@ -9,7 +9,7 @@
 // same exactness flags (no FMA contraction, IEEE div/sqrt).
 //
 // Level 0 is the depth-0 kernel (camera rays, camera buffer, light buffer)
-// with WAVE bit 512: a pixel whose hit spawns children writes a node record
+// with kWf0 (rt_variant.h): a pixel whose hit spawns children writes a node record
 // instead of its colour.  Level L >= 1 (rt_wf_level): each queued ray is
 // traced through the BVH, shaded, and either spawns children into level
 // L + 1 (a node record) or writes its colour.  Then the levels fold from the

@@ -166,3 +166,26 @@ def test_scene_host_build_under_asan_ubsan(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "scene_host_check: ok" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+def test_variant_selection_under_asan_ubsan(tmp_path):
+    """The trace kernels' variant word (csrc/rt_variant.h: the selection the
+    library compiles, its LDS sizes, kernel names and instantiation lists) in
+    a stand-alone host program built with AddressSanitizer and UBSan: every
+    variant the host can select is one the build instantiates, and the
+    selection gives the expected results tools/variant/variant_check.cpp
+    writes out."""
+    import subprocess
+
+    from conftest import REPO
+
+    exe = tmp_path / "variant_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-I", os.path.join(REPO, "ray-tracing-gpu_amd", "csrc"),
+                    os.path.join(REPO, "tools", "variant", "variant_check.cpp"), "-o", str(exe)],
+                   check=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "variant_check: ok" in r.stdout
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
