@@ -60,6 +60,13 @@ static bool cb_frame_ok(const rt_frame* f)
     return true;
 }
 
+// Frame f (reachable depth, light buffer on) may use a camera buffer; each
+// entry point adds its own terms (tiny scenes, cb_async_pays, a capture).
+static bool cb_wanted(const rt_ctx* c, const rt_frame* f, int depth, bool lbuf)
+{
+    return cam_lists(c, depth, lbuf) && c->n_tri > 0 && c->opt_camera_buffer && cb_frame_ok(f);
+}
+
 // Read back the last build's total and counters if its copy has landed
 // (no wait).
 static void cb_harvest(rt_ctx::CamBuf& B)

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cassert>
 #include <chrono>
 #include <cstdlib>
@@ -719,6 +720,19 @@ using namespace rt;
 constexpr int kSeqSlots = RT_SEQ_STREAMS;
 constexpr int kCbWordSets = 16;  // camera buffers per context: 1 + sequence slots (spare sets)
 
+struct rt_ctx;
+// A buffer that the context's streams share, one user at a time: a user on
+// another stream than the last one's waits for that one's event (enter), and
+// leaves its own behind (leave); after a host sync nobody is pending (done).
+struct Turn {
+    hipEvent_t ev = nullptr;  // after the last user (made by the first leave)
+    hipStream_t last = nullptr;
+    bool pending = false;
+    int enter(rt_ctx* c, hipStream_t st);
+    int leave(rt_ctx* c, hipStream_t st);
+    void done() { pending = false; }
+};
+
 struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
     int device = 0;
     // CPU backend (rt_create_cpu): no HIP object is ever made for it
@@ -734,16 +748,12 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
     float4* d_plane = nullptr;
     float4* d_quad = nullptr;
     int* d_translucent = nullptr;
-    float4* d_tricam = nullptr;
     float4* d_trisph = nullptr;
-    float4* d_cone_cam = nullptr;
     float4* d_cone_light = nullptr;
     float4* d_trinrm = nullptr;
     float4* d_tricoef = nullptr;
-    float4* d_clu_cam = nullptr;
     float4* d_clu_light = nullptr;
     int n_clu = 0;
-    float4* d_uni = nullptr;  // union records (small lists): camera, then one per light
     // A camera buffer (rt_cambuf.h): per-tile lists for the camera of key,
     // built on the stream that needs it; the entry array's capacity comes
     // from the totals of earlier builds, read back without a host sync
@@ -784,19 +794,28 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
         double host_ms = 0.0, build_ms = 0.0;
         bool timed = false;
     };
-    CamBuf cb;
+    // What one camera owns on the device: its records (cam_alloc: camera-ray
+    // triangle values, cone records, and the cluster records of a big list
+    // or the union records of a small one — the camera's, then one per
+    // light), its camera buffer, and the camera position the records were
+    // last computed for (camera_prepass; tricam_all: tricam holds every
+    // triangle for it).
+    struct CamState {
+        float4 *tricam = nullptr, *cone_cam = nullptr, *clu_cam = nullptr, *uni = nullptr;
+        CamBuf cb;
+        float key[3] = {0.f, 0.f, 0.f};
+        bool valid = false, tricam_all = false;
+    };
+    CamState cam;  // the camera of every entry point but the sequence's
     // the last async frame's camera (cb_key_of): a repeat builds the sorted lists
     float last_async_key[30] = {};
     bool last_async_valid = false;
-    // Camera state of rt_render_sequence_async: kSeqSlots slots of the
-    // per-camera records and camera buffers, apart from the state above;
-    // frame i of a sequence uses slot i % kSeqSlots on internal stream
-    // i % kSeqSlots, so up to kSeqSlots consecutive frames (different
-    // cameras) are in flight at once.
-    struct CamSlot {
-        float4 *tricam = nullptr, *cone_cam = nullptr, *clu_cam = nullptr, *uni = nullptr;
-        CamBuf cb;
-    } seq[kSeqSlots];
+    // The cameras of rt_render_sequence_async: frame i of a sequence uses
+    // slot i % kSeqSlots on internal stream i % kSeqSlots, so up to
+    // kSeqSlots consecutive frames (different cameras) are in flight at
+    // once.  A slot's records are computed for every frame: its key, valid
+    // and tricam_all stay unset.
+    CamState seq[kSeqSlots];
     hipStream_t seq_streams[kSeqSlots] = {};
     hipEvent_t seq_fork = nullptr, seq_join[kSeqSlots] = {};
     int n_cu = 0;
@@ -824,8 +843,6 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
     int lb_r0 = 0;      // light 0's first buffer's resolution (cells per face edge)
     size_t lb_entries = 0;
     double lb_build_ms = 0.0;
-    float cam_key[3] = {0.f, 0.f, 0.f};
-    bool cam_valid = false;
     // Tiny scenes (<= kTinyMax triangles, depth 0, light buffer): the camera
     // records are computed on the host per camera and passed with the launch
     // (rt_cull.h TinyCam) — host copies of the triangle records for that.
@@ -850,7 +867,6 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
     };
     std::vector<MaskBuf> tiny_masks;  // per stream, at most kMaskBufs
     unsigned long long mask_clock = 0;
-    bool tricam_all = false;  // tricam holds every triangle for cam_key
     StatsDev* d_stats = nullptr;
     void* d_scratch = nullptr;  // staging for host outputs
     size_t scratch_bytes = 0;
@@ -892,7 +908,7 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
     bool opt_bvh = true;        // RT_OPT_BVH
     // Wavefront bounce queues (rt_wavefront.h), grown on demand; one set per
     // context: a wavefront frame on another stream than the last one's waits
-    // for that frame (ev_wf) before it reuses them.
+    // for that frame (turn) before it reuses them.
     struct WfBuf {
         void* mem = nullptr;      // one allocation: counters, then every level's arrays
         size_t bytes = 0;
@@ -907,21 +923,17 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
         unsigned long long* bsum = nullptr;
         size_t kcap = 0, hcap = 0;
         int sort = 0;  // this frame's RT_OPT_WF_SORT: bit 0 parent sort, bit 1 hit sort (bit 2: by light cell)
-        hipEvent_t ev = nullptr;  // after the last wavefront frame
+        Turn turn;                // a wavefront frame at a time
         hipStream_t st2 = nullptr;               // RT_OPT_WF_OVERLAP: the stragglers' stream
         hipEvent_t ev_t = nullptr, ev_s = nullptr;  // fork (after the trace) / join (after the stragglers' shading)
-        hipStream_t last = nullptr;
-        bool pending = false;
     } wf;
     // Supersampled renders (rt_render_ss*): the float sample intermediate,
     // one per context, grown on demand: a call on another stream than the
-    // last one's waits for that call's resolve (ev) before it overwrites it.
+    // last one's waits for that call's resolve (turn) before it overwrites it.
     struct SsBuf {
         float* mem = nullptr;
         size_t bytes = 0;
-        hipEvent_t ev = nullptr;  // after the last resolve
-        hipStream_t last = nullptr;
-        bool pending = false;
+        Turn turn;  // left after a call's last resolve
     } ss;
     double opt_ss_chunk_rows = 0.0;  // RT_OPT_SS_CHUNK_ROWS (0 = auto)
     int opt_wavefront = 1;      // RT_OPT_WAVEFRONT
@@ -950,6 +962,28 @@ static int hip_fail(rt_ctx* c, hipError_t e, const char* what)
         hipError_t e_ = (call);                            \
         if (e_ != hipSuccess) return hip_fail(c, e_, #call); \
     } while (0)
+
+int Turn::enter(rt_ctx* c, hipStream_t st)
+{
+    if (pending && last != st) HIP_TRY(c, hipStreamWaitEvent(st, ev, 0));
+    return RT_OK;
+}
+int Turn::leave(rt_ctx* c, hipStream_t st)
+{
+    if (!ev) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(ev, st));
+    last = st;
+    pending = true;
+    return RT_OK;
+}
+
+// Every camera state of the context: its own, then the sequence slots'.
+static std::array<rt_ctx::CamState*, 1 + kSeqSlots> cam_states(rt_ctx* c)
+{
+    std::array<rt_ctx::CamState*, 1 + kSeqSlots> a{&c->cam};
+    for (int j = 0; j < kSeqSlots; ++j) a[1 + j] = &c->seq[j];
+    return a;
+}
 
 RT_EXPORT const char* rt_last_error(rt_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
@@ -1028,6 +1062,20 @@ static void note_async(rt_ctx* c, hipStream_t s)
         c->async_streams.push_back(s);
 }
 
+// The closing step of an entry point that enqueued on a caller's stream st.
+// In a capture the graph may reference the context's buffers from now on
+// (release, free_later) and pins the camera buffer it walks (`used`, or
+// null; cb_build); else uploads, fences and rt_destroy sync st.
+static void enqueued(rt_ctx* c, hipStream_t st, bool capturing, rt_ctx::CamBuf* used)
+{
+    if (capturing) {
+        c->captured = true;
+        if (used) used->pinned = true;
+    } else {
+        note_async(c, st);
+    }
+}
+
 // Buffers replaced while renders that read them may still have been in
 // flight (free_later): after a host sync of everything nothing reads them.
 // The internal sequence streams are joined into the caller's stream, which
@@ -1045,8 +1093,8 @@ static void settled(rt_ctx* c)
     c->async_streams.clear();
     c->state_pending = false;
     c->state_stream = nullptr;
-    c->wf.pending = false;
-    c->ss.pending = false;
+    c->wf.turn.done();
+    c->ss.turn.done();
     free_deferred(c);
 }
 
@@ -1091,7 +1139,7 @@ RT_EXPORT int rt_set_option(rt_ctx* c, int32_t opt, double v)
         return RT_OK;
     case RT_OPT_CAMERA_BUFFER:
         if (v != 0 && v != 1 && v != 2) return RT_E_ARG;
-        if ((int)v != c->opt_camera_buffer) c->cb.valid = false;
+        if ((int)v != c->opt_camera_buffer) c->cam.cb.valid = false;
         c->opt_camera_buffer = (int)v;
         return RT_OK;
     case RT_OPT_UNION_PRETEST: c->opt_union = v != 0; return RT_OK;
@@ -1106,7 +1154,7 @@ RT_EXPORT int rt_set_option(rt_ctx* c, int32_t opt, double v)
     case RT_OPT_CB_INLINE_MAX_MB:
         if (v < 0) return RT_E_ARG;
         // the layout is chosen at a camera-buffer build: rebuild at the next render
-        if (v != c->opt_cb_inline_mb) c->cb.valid = false;
+        if (v != c->opt_cb_inline_mb) c->cam.cb.valid = false;
         c->opt_cb_inline_mb = v;
         return RT_OK;
     case RT_OPT_HOST_CHUNK_MB:
@@ -1137,7 +1185,7 @@ RT_EXPORT int rt_set_option(rt_ctx* c, int32_t opt, double v)
         return RT_OK;
     case RT_OPT_CB_CAPACITY:
         if (v < 0 || v > 4e9 || v != std::floor(v)) return RT_E_ARG;
-        if (v != c->opt_cb_capacity) c->cb.valid = false;
+        if (v != c->opt_cb_capacity) c->cam.cb.valid = false;
         c->opt_cb_capacity = v;
         return RT_OK;
     default: return RT_E_ARG;
@@ -1228,14 +1276,14 @@ static void lb_drop(rt_ctx* c)
 static void scene_drop(rt_ctx* c)
 {
     c->uploaded = false;
-    free_all(c->d_geom, c->d_mat, c->d_lights, c->d_tri, c->d_plane, c->d_quad, c->d_translucent, c->d_tricam,
-             c->d_trisph, c->d_cone_cam, c->d_cone_light, c->d_trinrm, c->d_tricoef, c->d_clu_cam, c->d_clu_light,
-             c->d_uni, c->d_lrec, c->d_bvh_node, c->d_bvh_tri, c->d_skey);
+    free_all(c->d_geom, c->d_mat, c->d_lights, c->d_tri, c->d_plane, c->d_quad, c->d_translucent, c->d_trisph,
+             c->d_cone_light, c->d_trinrm, c->d_tricoef, c->d_clu_light, c->d_lrec, c->d_bvh_node, c->d_bvh_tri,
+             c->d_skey);
     lb_drop(c);
     c->lb_build_ms = 0.0;
-    for (auto& q : c->seq) {  // the sequence slots' per-camera records
-        free_all(q.tricam, q.cone_cam, q.clu_cam, q.uni);
-        q.cb.valid = false;
+    for (rt_ctx::CamState* q : cam_states(c)) {  // the per-camera records
+        free_all(q->tricam, q->cone_cam, q->clu_cam, q->uni);
+        q->cb.valid = q->valid = false;
     }
     for (auto* h : {&c->h_lrec, &c->h_tri, &c->h_sph, &c->h_nrm, &c->h_coef}) h->clear();
     c->h_plane.clear();
@@ -1243,8 +1291,6 @@ static void scene_drop(rt_ctx* c)
     c->nbin_half = 0;
     c->bvh_inner = c->bvh_leaves = c->bvh_depth = 0;
     c->bvh_build_ms = 0.0;
-    c->cb.valid = false;
-    c->cam_valid = false;
     c->tiny_valid = false;
     for (auto& q : c->tiny_masks) q.valid = q.pend_valid = false;  // the old scene's triangles
     static_cast<SceneCounts&>(*c) = SceneCounts{};
@@ -1271,8 +1317,8 @@ RT_EXPORT void rt_destroy(rt_ctx* c)
     hipFree(c->wf.hist);
     hipFree(c->wf.bsum);
     hipFree(c->ss.mem);
-    if (c->ss.ev) hipEventDestroy(c->ss.ev);
-    if (c->wf.ev) hipEventDestroy(c->wf.ev);
+    if (c->ss.turn.ev) hipEventDestroy(c->ss.turn.ev);
+    if (c->wf.turn.ev) hipEventDestroy(c->wf.turn.ev);
     if (c->wf.ev_t) hipEventDestroy(c->wf.ev_t);
     if (c->wf.ev_s) hipEventDestroy(c->wf.ev_s);
     if (c->wf.st2) hipStreamDestroy(c->wf.st2);
@@ -1280,8 +1326,7 @@ RT_EXPORT void rt_destroy(rt_ctx* c)
         hipFree(q.d);
         if (q.ev) hipEventDestroy(q.ev);
     }
-    cb_free(c->cb);
-    for (auto& q : c->seq) cb_free(q.cb);
+    for (rt_ctx::CamState* q : cam_states(c)) cb_free(q->cb);
     hipFree(c->d_stats);
     hipFree(c->d_scratch);
     if (c->ev0) hipEventDestroy(c->ev0);
@@ -1624,8 +1669,8 @@ static void lb_meta_words(const float4& m, unsigned& obase, int& R)
     std::memcpy(&R, &m.w, 4);
 }
 
-// The per-kind lists and per-triangle records, the buffers of the camera's
-// and the lights' cone records, and the tiny scenes' host copies.
+// The per-kind lists and per-triangle records, the buffer of the lights'
+// cone records, and the tiny scenes' host copies.
 static int upload_records(rt_ctx* c, const SceneHost& H)
 {
     const size_t ntr = H.ntr;
@@ -1633,11 +1678,9 @@ static int upload_records(rt_ctx* c, const SceneHost& H)
     HIP_TRY(c, up(&c->d_plane, H.pla));
     HIP_TRY(c, up(&c->d_quad, H.qua));
     HIP_TRY(c, up(&c->d_translucent, H.translucent));
-    HIP_TRY(c, hipMalloc((void**)&c->d_tricam, ntr * 16 * sizeof(float)));
     HIP_TRY(c, up(&c->d_trisph, H.sph));
     HIP_TRY(c, up(&c->d_trinrm, H.nrm));
     HIP_TRY(c, up(&c->d_tricoef, H.coef));
-    HIP_TRY(c, hipMalloc((void**)&c->d_cone_cam, ntr * kConeRec * sizeof(float4)));
     HIP_TRY(c, hipMalloc((void**)&c->d_cone_light, std::max<size_t>(ntr * H.n_lights, 1) * kConeRec * sizeof(float4)));
     c->h_plane = H.pla;
     if (ntr <= (size_t)kTinyMax) {  // the launch-camera path's host records
@@ -1690,9 +1733,26 @@ static double dcov_factor(const rt_ctx* c, const SceneHost& H)
     return c->opt_dcov_near > 0.0 ? c->opt_dcov_near : RT_DCOV_FACTOR;
 }
 
+// One camera's record buffers for scene H (c->n_clu is set): every
+// triangle's camera record (the camera-buffer walk reads them) and cone
+// records, and the cluster records of a big list or the union records of a
+// small one.
+static int cam_alloc(rt_ctx* c, rt_ctx::CamState& q, const SceneHost& H)
+{
+    HIP_TRY(c, hipMalloc((void**)&q.tricam, H.ntr * 4 * sizeof(float4)));
+    HIP_TRY(c, hipMalloc((void**)&q.cone_cam, H.ntr * kConeRec * sizeof(float4)));
+    if (c->n_clu > 0)
+        HIP_TRY(c, hipMalloc((void**)&q.clu_cam, (size_t)c->n_clu * 4 * sizeof(float4)));
+    else
+        HIP_TRY(c, hipMalloc((void**)&q.uni, (size_t)(H.n_lights + 1) * 2 * sizeof(float4)));
+    return RT_OK;
+}
+
 // The lights' prepasses: every light's cone records for its distance
 // dcov[j], then the cluster records of a big list or the union records of a
-// small one ([camera (filled when the camera is set)] [light 0] ...).
+// small one ([camera (filled when the camera is set)] [light 0] ...), whose
+// light part is computed once and copied to the sequence slots.  The camera
+// states' buffers are allocated here (the list's kind decides which).
 static int light_prepasses(rt_ctx* c, const SceneHost& H, std::vector<double>& dcov)
 {
     hipStream_t st = c->stream;
@@ -1705,9 +1765,10 @@ static int light_prepasses(rt_ctx* c, const SceneHost& H, std::vector<double>& d
         if (int rc = launch_light_cones(c, H, j, d, c->d_cone_light + kConeRec * ntr * j)) return rc;
         dcov[(size_t)j] = (double)d;
     }
-    if (ntr > (size_t)kClusterMinTriangles) {
-        c->n_clu = (int)((ntr + 63) / 64);
-        HIP_TRY(c, hipMalloc((void**)&c->d_clu_cam, (size_t)c->n_clu * 4 * sizeof(float4)));
+    c->n_clu = ntr > (size_t)kClusterMinTriangles ? (int)((ntr + 63) / 64) : 0;
+    for (rt_ctx::CamState* q : cam_states(c))
+        if (int rc = cam_alloc(c, *q, H)) return rc;
+    if (c->n_clu > 0) {
         HIP_TRY(c, hipMalloc((void**)&c->d_clu_light, std::max<size_t>((size_t)c->n_clu * nl, 1) * 2 * sizeof(float4)));
         for (int j = 0; j < nl; ++j) {
             hipLaunchKernelGGL(rt_cluster_prepass, dim3(cluster_blocks(c->n_clu)), dim3(256), 0, st,
@@ -1717,10 +1778,10 @@ static int light_prepasses(rt_ctx* c, const SceneHost& H, std::vector<double>& d
         }
         return RT_OK;
     }
-    HIP_TRY(c, hipMalloc((void**)&c->d_uni, (size_t)(nl + 1) * 2 * sizeof(float4)));
+    float4* const uni = c->cam.uni;
     for (int j = 0; j < nl && n_tri_o > 0; ++j) {
         hipLaunchKernelGGL(rt_cluster_prepass, dim3(1), dim3(64), 0, st, c->d_cone_light + kConeRec * ntr * j, n_tri_o,
-                           1, c->d_uni + 2 * (1 + (size_t)j), n_tri_o);  // one wave
+                           1, uni + 2 * (1 + (size_t)j), n_tri_o);  // one wave
         HIP_TRY(c, hipGetLastError());
     }
     if (n_tri_o == 0) {  // no opaque triangle: nothing for shadow rays to walk ("never" record)
@@ -1729,27 +1790,11 @@ static int light_prepasses(rt_ctx* c, const SceneHost& H, std::vector<double>& d
             nev[2 * j] = make_float4(0.f, 0.f, 0.f, 2.0f);
             nev[2 * j + 1] = make_float4(INFINITY, 0.f, INFINITY, 0.f);
         }
-        if (nl) HIP_TRY(c, hipMemcpyAsync(c->d_uni + 2, nev.data(), nev.size() * sizeof(float4), hipMemcpyHostToDevice, st));
+        if (nl) HIP_TRY(c, hipMemcpyAsync(uni + 2, nev.data(), nev.size() * sizeof(float4), hipMemcpyHostToDevice, st));
         HIP_TRY(c, hipStreamSynchronize(st));  // nev outlives the copy
     }
-    return RT_OK;
-}
-
-// The sequence slots (rt_render_sequence_async): per-camera records of
-// their own; the union records' light part is the scene's.
-static int alloc_seq_slots(rt_ctx* c, const SceneHost& H)
-{
-    const size_t ntr = H.ntr, uni = (size_t)(H.n_lights + 1) * 2 * sizeof(float4);
-    for (auto& q : c->seq) {
-        // every triangle's camera record: the camera-buffer walk reads them
-        HIP_TRY(c, hipMalloc((void**)&q.tricam, ntr * 4 * sizeof(float4)));
-        HIP_TRY(c, hipMalloc((void**)&q.cone_cam, ntr * kConeRec * sizeof(float4)));
-        if (c->n_clu > 0) HIP_TRY(c, hipMalloc((void**)&q.clu_cam, (size_t)c->n_clu * 4 * sizeof(float4)));
-        if (c->d_uni) {
-            HIP_TRY(c, hipMalloc((void**)&q.uni, uni));
-            HIP_TRY(c, hipMemcpyAsync(q.uni, c->d_uni, uni, hipMemcpyDeviceToDevice, c->stream));
-        }
-    }
+    for (auto& q : c->seq)
+        HIP_TRY(c, hipMemcpyAsync(q.uni, uni, (size_t)(nl + 1) * 2 * sizeof(float4), hipMemcpyDeviceToDevice, st));
     return RT_OK;
 }
 
@@ -1870,7 +1915,6 @@ RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
     const auto tp0 = std::chrono::steady_clock::now();
     std::vector<double> dcov;  // per light: its (first) buffer's distance
     if (int rc = light_prepasses(c, H, dcov)) return rc;
-    if (int rc = alloc_seq_slots(c, H)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->upload_parts_ms[1] = ms_since(tp0);
     const auto tl0 = std::chrono::steady_clock::now();
@@ -2053,71 +2097,73 @@ static void frame_dev(const rt_frame* f, FrameDev& F)
     F.wf = WfDev{};
 }
 
-// Does frame f need the per-camera prepasses (the camera position moved)?
-// A camera already prepared without every tricam record — a bounce frame
-// of a big scene — is prepared again for the camera buffer.
-static bool camera_needs_prepass(const rt_ctx* c, const rt_frame* f, bool all_tricam)
+// Does frame f need the per-camera prepasses (the camera position moved
+// from the one cam's records are for)?  A camera already prepared without
+// every tricam record — a bounce frame of a big scene — is prepared again
+// for the camera buffer.
+static bool camera_needs_prepass(const rt_ctx* c, const rt_ctx::CamState& cam, const rt_frame* f, bool all_tricam)
 {
-    return c->n_tri > 0 && !(c->cam_valid && std::memcmp(c->cam_key, f->cam_pos, sizeof c->cam_key) == 0 &&
-                             (!all_tricam || c->tricam_all));
+    return c->n_tri > 0 && !(cam.valid && std::memcmp(cam.key, f->cam_pos, sizeof cam.key) == 0 &&
+                             (!all_tricam || cam.tricam_all));
 }
 
-// The per-camera records of camera position cp into one set of buffers:
+// The per-camera records of camera position cp into cam's buffers:
 // camera-ray triangle values, camera cone records, union / cluster records.
-static int camera_records(rt_ctx* c, const float* cp, hipStream_t st, bool all_tricam, float4* tricam,
-                          float4* cone_cam, float4* uni, float4* clu_cam)
+static int camera_records(rt_ctx* c, rt_ctx::CamState& cam, const float* cp, hipStream_t st, bool all_tricam)
 {
-    float4* tc = (all_tricam || c->n_tri <= kTricamMaxTriangles) ? tricam : nullptr;
-    if (uni && c->n_clu == 0 && c->n_tri <= kCameraSmallMax) {  // small lists: one launch
+    float4* const cone_cam = cam.cone_cam;
+    float4* tc = (all_tricam || c->n_tri <= kTricamMaxTriangles) ? cam.tricam : nullptr;
+    if (cam.uni && c->n_clu == 0 && c->n_tri <= kCameraSmallMax) {  // small lists: one launch
         hipLaunchKernelGGL(rt_camera_small, dim3(1), dim3(256), 0, st, c->d_tri, c->d_trisph, c->d_trinrm,
-                           c->d_tricoef, c->n_tri, cp[0], cp[1], cp[2], cone_cam, tc, uni);
+                           c->d_tricoef, c->n_tri, cp[0], cp[1], cp[2], cone_cam, tc, cam.uni);
         HIP_TRY(c, hipGetLastError());
         return RT_OK;
     }
     hipLaunchKernelGGL(rt_cone_prepass, dim3((c->n_tri + 255) / 256), dim3(256), 0, st, c->d_tri, c->d_trisph,
                        c->d_trinrm, c->d_tricoef, c->n_tri, cp[0], cp[1], cp[2], 1, 0.0f, cone_cam, tc);
     HIP_TRY(c, hipGetLastError());
-    if (uni) {
-        hipLaunchKernelGGL(rt_cluster_prepass, dim3(1), dim3(64), 0, st, cone_cam, c->n_tri, 1, uni, c->n_tri);  // one wave
+    if (cam.uni) {
+        hipLaunchKernelGGL(rt_cluster_prepass, dim3(1), dim3(64), 0, st, cone_cam, c->n_tri, 1, cam.uni, c->n_tri);  // one wave
         HIP_TRY(c, hipGetLastError());
     }
     if (c->n_clu > 0) {
-        float4* tmp = clu_cam + 2 * (size_t)c->n_clu;  // second half: unsorted
+        float4* tmp = cam.clu_cam + 2 * (size_t)c->n_clu;  // second half: unsorted
         hipLaunchKernelGGL(rt_cluster_prepass, dim3(cluster_blocks(c->n_clu)), dim3(256), 0, st, cone_cam,
                            c->n_tri, c->n_clu, tmp, 64);
         HIP_TRY(c, hipGetLastError());
         hipLaunchKernelGGL(rt_cluster_sort, dim3(cluster_blocks(c->n_clu)), dim3(256), 0, st, tmp,
-                           c->n_clu, clu_cam);
+                           c->n_clu, cam.clu_cam);
         HIP_TRY(c, hipGetLastError());
     }
     return RT_OK;
 }
 
-// Per-camera prepasses (when the camera position moved), into the
-// context's state.
-static int camera_prepass(rt_ctx* c, const rt_frame* f, hipStream_t st, bool all_tricam)
+// Per-camera prepasses (when the camera position moved) into cam, whose
+// camera buffer they make stale.
+static int camera_prepass(rt_ctx* c, rt_ctx::CamState& cam, const rt_frame* f, hipStream_t st, bool all_tricam)
 {
-    if (!camera_needs_prepass(c, f, all_tricam)) return RT_OK;
-    if (int rc = camera_records(c, f->cam_pos, st, all_tricam, c->d_tricam, c->d_cone_cam, c->d_uni, c->d_clu_cam))
-        return rc;
-    std::memcpy(c->cam_key, f->cam_pos, sizeof c->cam_key);
-    c->cam_valid = true;
-    c->tricam_all = all_tricam || c->n_tri <= kTricamMaxTriangles;
-    c->cb.valid = false;
+    if (!camera_needs_prepass(c, cam, f, all_tricam)) return RT_OK;
+    if (int rc = camera_records(c, cam, f->cam_pos, st, all_tricam)) return rc;
+    std::memcpy(cam.key, f->cam_pos, sizeof cam.key);
+    cam.valid = true;
+    cam.tricam_all = all_tricam || c->n_tri <= kTricamMaxTriangles;
+    cam.cb.valid = false;
     return RT_OK;
 }
 
-static SceneDev scene_dev(rt_ctx* c, bool lbuf, bool cbuf)
+// The kernels' view of the scene, its camera-dependent fields from cam
+// (cbuf: the launch walks cam's camera buffer).
+static SceneDev scene_dev(const rt_ctx* c, const rt_ctx::CamState& cam, bool lbuf, bool cbuf)
 {
     const int use_tricam = c->n_tri > 0 && c->n_tri <= kTricamMaxTriangles;
-    return SceneDev{c->d_geom, c->d_mat, c->d_lights, c->d_tri, c->d_plane, c->d_quad, c->d_translucent, c->d_tricam,
-                    use_tricam, c->n_tri <= kEdgeMaxTriangles, c->d_cone_cam, c->d_cone_light, c->d_clu_cam,
+    return SceneDev{c->d_geom, c->d_mat, c->d_lights, c->d_tri, c->d_plane, c->d_quad, c->d_translucent, cam.tricam,
+                    use_tricam, c->n_tri <= kEdgeMaxTriangles, cam.cone_cam, c->d_cone_light, cam.clu_cam,
                     c->d_clu_light, c->n_clu, c->n_surf, c->n_lights, c->n_tri, c->n_plane, c->n_quad,
                     c->n_tri_opaque, c->n_plane_opaque, c->n_quad_opaque, c->n_translucent, c->shadow_split,
                     lbuf ? c->lb_levels : 0, c->d_lb_off, c->d_lb_ent, c->d_lb_dcap, c->d_lb_meta,
-                    (c->d_uni && c->opt_union) ? c->d_uni : nullptr,
-                    c->cb.off, c->cb.ent, c->cb.flag, cbuf ? c->cb.tiles_x : 0,
-                    c->cb.inline_rec ? c->cb.rec : nullptr, c->d_bvh_node, c->d_bvh_tri};
+                    (cam.uni && c->opt_union) ? cam.uni : nullptr,
+                    cam.cb.off, cam.cb.ent, cam.cb.flag, cbuf ? cam.cb.tiles_x : 0,
+                    cam.cb.inline_rec ? cam.cb.rec : nullptr, c->d_bvh_node, c->d_bvh_tri};
 }
 
 // The light buffer serves this context's shadow rays (RT_OPT_LIGHT_BUFFER).
@@ -2142,8 +2188,9 @@ static bool cam_lists(const rt_ctx* c, int depth, bool lbuf) { return depth == 0
 
 #include "rt_camhost.h"
 
-// Make the per-camera state current for frame f, ordered on stream st: the
-// camera prepass when the camera moved, and the camera buffer when the
+// Make the per-camera state cam current for frame f, ordered on stream st
+// (cam is the context's own: state_pending, ev_state and last_async_key
+// order and remember that one): the camera prepass when the camera moved, and the camera buffer when the
 // frame's kernel uses one and it is not current.  sync_path: a synchronous
 // call on c->stream (fenced behind every async render at its start).
 // Async (round 3: the camera buffer too, no host sync): a write fences st
@@ -2151,7 +2198,8 @@ static bool cam_lists(const rt_ctx* c, int depth, bool lbuf) { return depth == 0
 // otherwise st waits for a pending write made on another stream.
 // Capturing: nothing may be written (an unprepared camera is RT_E_STATE; a
 // prepared camera whose buffer is not current renders without it).
-static int prepare_state(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync_path, bool capturing, bool cb_want)
+static int prepare_state(rt_ctx* c, rt_ctx::CamState& cam, const rt_frame* f, hipStream_t st, bool sync_path,
+                         bool capturing, bool cb_want)
 {
     if (capturing && c->state_pending && c->state_stream != st) {
         // a wait on an event recorded outside the capture cannot be captured
@@ -2162,8 +2210,8 @@ static int prepare_state(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync
     if (!sync_path && !capturing) {
         if (int rc = wait_state(c, st)) return rc;
     }
-    if (!capturing) cb_harvest(c->cb);
-    const bool need_prep = camera_needs_prepass(c, f, cb_want);
+    if (!capturing) cb_harvest(cam.cb);
+    const bool need_prep = camera_needs_prepass(c, cam, f, cb_want);
     // The camera buffer is built by a synchronous render, by an async frame
     // repeating the previous async frame's camera (round 4: a static camera
     // rendered async gets its lists at its second frame), and by a new
@@ -2175,7 +2223,7 @@ static int prepare_state(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync
         std::memcpy(c->last_async_key, key, sizeof key);
         c->last_async_valid = true;
     }
-    const bool current = cb_matches(c->cb, f) && !need_prep;
+    const bool current = cb_matches(cam.cb, f) && !need_prep;
     const bool need_cb = cb_want && !current && (sync_path || repeat || cb_async_pays(c, f));
     if (capturing) {
         if (need_prep) {
@@ -2189,11 +2237,11 @@ static int prepare_state(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync
         if (int rc = fence_async(c, st)) return rc;
     }
     if (need_prep) {
-        if (int rc = camera_prepass(c, f, st, cb_want)) return rc;
+        if (int rc = camera_prepass(c, cam, f, st, cb_want)) return rc;
     }
     if (need_cb) {
-        const SceneDev S = scene_dev(c, false, false);
-        if (int rc = cb_build(c, c->cb, f, S, st, sync_path, false, true)) return rc;
+        const SceneDev S = scene_dev(c, cam, false, false);
+        if (int rc = cb_build(c, cam.cb, f, S, st, sync_path, false, true)) return rc;
     }
     if (!sync_path) {
         HIP_TRY(c, hipEventRecord(c->ev_state, st));
@@ -2334,7 +2382,6 @@ static int wf_ensure(rt_ctx* c, const rt_frame* f, int rows, int levels, bool ca
         HIP_TRY(c, hipMalloc(&W.mem, w.bytes));
         W.bytes = w.bytes;
     }
-    if (!W.ev) HIP_TRY(c, hipEventCreateWithFlags(&W.ev, hipEventDisableTiming));
     char* p = (char*)W.mem;
     auto take = [&](size_t bytes) {
         char* q = p;
@@ -2681,10 +2728,31 @@ struct FramePlan {
     FrameDev F;
 };
 
-// Plans frame f for stream st, into P (filled in place: TinyCam and SceneDev
-// are large).  What the plan needs on the device is enqueued or allocated
-// here: the tile masks' buffer, the per-camera state, the wavefront queues,
-// the sample intermediate.  Fills c->last.
+// The second half of every colour frame's plan.  The caller has decided
+// P.depth, lbuf, bvh, tiny, tmode, cbuf and wf by its own rules; from them,
+// the camera state the kernel reads and the caller's own fact `small`
+// (Facts::small): the kernel and its arguments, P.kp, P.S and P.F.
+static int plan_kernel(rt_ctx* c, const rt_frame* f, const rt_ctx::CamState& cam, bool small, FramePlan& P)
+{
+    Facts fa = frame_facts(c, f, P.depth, P.lbuf, P.cbuf, P.bvh);
+    fa.small = small;
+    fa.wf0 = P.wf;
+    fa.tiny = P.tiny ? P.tmode : -1;
+    P.kp = pick_kernel(fa, (f->flags & RT_FLAG_STATS) != 0);
+    if (!P.kp.k) {
+        c->err = "reachable bounce depth " + std::to_string(P.depth) + " exceeds the compiled stack (32)";
+        return RT_E_UNSUPPORTED;
+    }
+    P.S = scene_dev(c, cam, P.lbuf, P.cbuf);
+    frame_dev(f, P.F);
+    if (P.wf) P.F.wf = c->wf.dev;
+    return RT_OK;
+}
+
+// Plans frame f of the context's camera for stream st, into P (filled in
+// place: TinyCam and SceneDev are large).  What the plan needs on the device
+// is enqueued or allocated here: the tile masks' buffer, the per-camera
+// state, the wavefront queues, the sample intermediate.  Fills c->last.
 // ss > 1: a supersampled render — the samples go to c->ss, one chunk at a
 // time; px_bytes, host_out: the output's bytes per pixel and whether launch
 // copies it to the host (rt_chunks.h).
@@ -2694,7 +2762,7 @@ static int plan_frame(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync_pa
     const int depth = P.depth = reachable_depth(c, f);
     const bool lbuf = P.lbuf = lbuf_on(c);
     const bool bvh = P.bvh = bvh_on(c, depth, lbuf);
-    const bool cb_want = cam_lists(c, depth, lbuf) && c->n_tri > 0 && c->opt_camera_buffer && cb_frame_ok(f);
+    const bool cb_want = cb_wanted(c, f, depth, lbuf);
     const int rows = P.rows = frame_rows(f);
     // tiny scenes: the camera records travel with the launch (no device state)
     P.tmode = 0;
@@ -2705,9 +2773,9 @@ static int plan_frame(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync_pa
             if (int rc = tiny_masks(c, f, st, capturing, P.T, &P.tmode)) return rc;
     }
     if (rows > 0 && !P.tiny) {
-        if (int rc = prepare_state(c, f, st, sync_path, capturing, cb_want)) return rc;
+        if (int rc = prepare_state(c, c->cam, f, st, sync_path, capturing, cb_want)) return rc;
     }
-    const bool cbuf = P.cbuf = !P.tiny && cb_want && cb_matches(c->cb, f);
+    P.cbuf = !P.tiny && cb_want && cb_matches(c->cam.cb, f);
     // Wavefront: a BVH frame's bounce levels as compacted queues (rt_wavefront.h);
     // its queues are shared by the context's streams: a frame on another
     // stream than the last wavefront frame waits for that one.  A captured
@@ -2742,21 +2810,9 @@ static int plan_frame(rt_ctx* c, const rt_frame* f, hipStream_t st, bool sync_pa
             HIP_TRY(c, hipMalloc((void**)&B.mem, need));
             B.bytes = need;
         }
-        if (!B.ev) HIP_TRY(c, hipEventCreateWithFlags(&B.ev, hipEventDisableTiming));
     }
-    const bool count = (f->flags & RT_FLAG_STATS) != 0;
-    Facts fa = frame_facts(c, f, depth, lbuf, cbuf, bvh);
-    fa.small = small_frame((double)f->width * rows) && c->opt_lb_unroll;
-    fa.wf0 = wf;
-    fa.tiny = P.tiny ? P.tmode : -1;
-    const KernelPick& kp = P.kp = pick_kernel(fa, count);
-    if (!kp.k) {
-        c->err = "reachable bounce depth " + std::to_string(depth) + " exceeds the compiled stack (32)";
-        return RT_E_UNSUPPORTED;
-    }
-    P.S = scene_dev(c, lbuf, cbuf);
-    frame_dev(f, P.F);
-    if (wf) P.F.wf = c->wf.dev;
+    if (int rc = plan_kernel(c, f, c->cam, small_frame((double)f->width * rows) && c->opt_lb_unroll, P)) return rc;
+    const KernelPick& kp = P.kp;
     c->last = rt_stats{};
     c->last.stack_depth = wf ? depth : kp.v.maxd;
     c->last.light_batch = kp.v.lb;
@@ -2795,13 +2851,14 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
     StatsDev* stats = c->d_stats;
     if (P.wf) {
         rt_ctx::WfBuf& W = c->wf;
-        if (W.pending && W.last != st) HIP_TRY(c, hipStreamWaitEvent(st, W.ev, 0));
+        if (int rc = W.turn.enter(c, st)) return rc;
         HIP_TRY(c, hipMemsetAsync(W.dev.count, 0, kWfCountBytes, st));
         if (W.sort)  // the bin counts (level 1's: the level-0 kernel's appends)
             HIP_TRY(c, hipMemsetAsync(W.dev.hist, 0, 2 * W.hcap * sizeof(unsigned), st));
     }
     rt_ctx::SsBuf& B = c->ss;
-    if (P.ss_staged && B.pending && B.last != st && !capturing) HIP_TRY(c, hipStreamWaitEvent(st, B.ev, 0));
+    if (P.ss_staged && !capturing)
+        if (int rc = B.turn.enter(c, st)) return rc;
     // every chunk's kernel first, then the copies (a copy into pageable
     // memory blocks the host; the kernels behind it keep running)
     const bool host_chunked = host_out && step < rows;
@@ -2822,9 +2879,7 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
             return rc;
         if (P.wf) {  // (one chunk)
             if (int rc = wf_levels(c, P.S, *F, P.depth, count, oa, ob, stats, st)) return rc;
-            HIP_TRY(c, hipEventRecord(c->wf.ev, st));
-            c->wf.last = st;
-            c->wf.pending = true;
+            if (int rc = c->wf.turn.leave(c, st)) return rc;
         }
         if (P.ss_staged) {  // the chunk's rows inside the frame
             const int q0 = r0 / ss, nq = (std::max(r0, std::min(r1, vrows)) - r0) / ss;
@@ -2839,11 +2894,8 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
     }
     if (P.tmode == 2)
         if (int rc = tiny_masks_stored(c, st)) return rc;
-    if (P.ss_staged && !capturing) {
-        HIP_TRY(c, hipEventRecord(B.ev, st));
-        B.last = st;
-        B.pending = true;
-    }
+    if (P.ss_staged && !capturing)
+        if (int rc = B.turn.leave(c, st)) return rc;
     const char* src = (const char*)(rgba_dev ? (void*)rgba_dev : (void*)rgb_dev);
     if (host_chunked) {
         if (timed) HIP_TRY(c, hipEventRecord(c->ev1, st));
@@ -2859,12 +2911,7 @@ static int launch(rt_ctx* c, const rt_frame* f, unsigned* rgba_dev, float* rgb_d
         HIP_TRY(c, hipMemcpyAsync(host_out, src, (size_t)rows * f->width * px_bytes, hipMemcpyDeviceToHost, st));
     }
     if (timed) HIP_TRY(c, hipEventRecord(c->ev1, st));
-    if (capturing) {
-        c->captured = true;
-        if (P.cbuf) c->cb.pinned = true;
-    } else if (!sync_path) {  // (uploads and rt_destroy sync every such stream)
-        note_async(c, st);
-    }
+    if (!sync_path) enqueued(c, st, capturing, P.cbuf ? &c->cam.cb : nullptr);
     return RT_OK;
 }
 
@@ -3003,6 +3050,32 @@ RT_EXPORT int rt_render_async(rt_ctx* c, const rt_frame* f, uint8_t* rgba8_dev, 
     return launch(c, f, (unsigned*)rgba8_dev, rgb_dev, (hipStream_t)stream, false, false);
 }
 
+// A camera path: frame i with the camera state of slot i % kSeqSlots on
+// internal stream i % nstreams, forked from and joined back into the
+// caller's stream.  The frames' plans are made here, not by plan_frame: its
+// first half is about the context's one camera (tiny_prepare's cache,
+// prepare_state's ordering of c->cam across the caller's streams, the
+// wavefront queues), and a path of new cameras wants none of that.  The
+// second half (plan_kernel) is shared.  What a sequence frame does
+// differently from the same frame through rt_render_async:
+//  * its camera records are computed for every frame, into its slot, with
+//    every tricam record exactly when the frame builds a camera buffer; the
+//    slot keeps no camera key (CamState::valid stays false);
+//  * TinyCam is built into the plan (tiny_build), not through c->tiny's
+//    cache; the tile masks are per internal stream (tiny_masks);
+//  * the camera buffer is built only where cb_async_pays says so (no
+//    "repeated camera" rule), inside a capture only into arrays already
+//    sized, never sized exactly first and never with inline records (so
+//    SceneDev::cb_rec is null: CamBuf::inline_rec stays false);
+//  * it never runs as a wavefront (a bounce frame takes the BVH megakernel)
+//    and sets neither Facts::wf0 nor Facts::small.  The missing `small` is
+//    an inconsistency nobody measured: a big-list frame under 4 Mpx runs the
+//    kernel without kLbPair here and the kLbPair one through rt_render_async
+//    (rt_variant.h).  Left as it is for a change that measures it;
+//  * c->last is not written (no stats of a sequence), c->cam and
+//    last_async_key are not touched;
+//  * the call is fenced behind the context's other async work once, at its
+//    start, not per frame, and every frame is checked before any is enqueued.
 RT_EXPORT int rt_render_sequence_async(rt_ctx* c, const rt_frame* frames, int32_t n, uint8_t* rgba8_dev,
                                        size_t rgba8_stride, float* rgb_dev, size_t rgb_stride, void* stream)
 {
@@ -3044,55 +3117,44 @@ RT_EXPORT int rt_render_sequence_async(rt_ctx* c, const rt_frame* frames, int32_
         HIP_TRY(c, hipEventRecord(c->seq_fork, st));
         for (int j = 0; j < nstreams; ++j) HIP_TRY(c, hipStreamWaitEvent(c->seq_streams[j], c->seq_fork, 0));
     }
+    FramePlan P;  // (one chunk each, never supersampled: step and ss_staged stay unused)
+    P.wf = false;
     for (int i = 0; i < n; ++i) {
         const rt_frame* f = frames + i;
-        rt_ctx::CamSlot& q = c->seq[i % kSeqSlots];
+        rt_ctx::CamState& q = c->seq[i % kSeqSlots];
         hipStream_t fs = nstreams > 1 ? c->seq_streams[i % nstreams] : st;
-        const int rows = frame_rows(f);
+        const int rows = P.rows = frame_rows(f);
         if (rows == 0) continue;
-        const int depth = reachable_depth(c, f);
+        const int depth = P.depth = reachable_depth(c, f);
+        P.lbuf = lbuf;
+        P.bvh = bvh_on(c, depth, lbuf);
+        P.tmode = 0;
+        P.tiny = tiny_ok(c, depth, lbuf);
+        if (P.tiny) {
+            tiny_build(c, f, P.T);
+            if (int rc = tiny_masks(c, f, fs, capturing, P.T, &P.tmode)) return rc;
+        }
         // the slot's camera buffer (round 3, big lists as for rt_render_async):
         // built on the frame's stream like its records; inside a capture only
         // into buffers already sized (a first capture renders without it —
         // the same image)
         const int nt = ((f->width + 7) / 8) * ((f->height + 7) / 8);
-        TinyCam T;
-        int tmode = 0;
-        const bool tiny = tiny_ok(c, depth, lbuf);
-        if (tiny) {
-            tiny_build(c, f, T);
-            if (int rc = tiny_masks(c, f, fs, capturing, T, &tmode)) return rc;
+        const bool cbuf = P.cbuf =
+            !P.tiny && cb_wanted(c, f, depth, lbuf) && cb_async_pays(c, f) &&
+            (!capturing || (q.cb.cap > 0 && q.cb.rcap > 0 && q.cb.nt_alloc >= nt && q.cb.big_alloc >= c->n_tri));
+        if (c->n_tri > 0 && !P.tiny) {
+            if (int rc = camera_records(c, q, f->cam_pos, fs, cbuf)) return rc;
         }
-        const bool bvh = bvh_on(c, depth, lbuf);
-        const bool cbuf = !tiny && cam_lists(c, depth, lbuf) && c->n_tri > 0 && c->opt_camera_buffer && cb_frame_ok(f) &&
-                          cb_async_pays(c, f) &&
-                          (!capturing || (q.cb.cap > 0 && q.cb.rcap > 0 && q.cb.nt_alloc >= nt && q.cb.big_alloc >= c->n_tri));
-        if (c->n_tri > 0 && !tiny) {
-            if (int rc = camera_records(c, f->cam_pos, fs, cbuf, q.tricam, q.cone_cam, q.uni, q.clu_cam)) return rc;
-        }
-        Facts fa = frame_facts(c, f, depth, lbuf, cbuf, bvh);
-        fa.tiny = tiny ? tmode : -1;
-        const KernelPick kp = pick_kernel(fa, false);
-        SceneDev S = scene_dev(c, lbuf, false);
-        S.tricam = q.tricam;
-        S.cone_cam = q.cone_cam;
-        S.clu_cam = q.clu_cam;
-        S.uni = (q.uni && c->opt_union) ? q.uni : nullptr;
         if (cbuf) {
+            const SceneDev S = scene_dev(c, q, false, false);
             if (int rc = cb_build(c, q.cb, f, S, fs, false, capturing, false)) return rc;
-            S.cb_off = q.cb.off;
-            S.cb_ent = q.cb.ent;
-            S.cb_flag = q.cb.flag;
-            S.cb_tiles_x = q.cb.tiles_x;
-            S.cb_rec = nullptr;
         }
-        FrameDev F;
-        frame_dev(f, F);
+        if (int rc = plan_kernel(c, f, q, false, P)) return rc;
         unsigned* rgba = rgba8_dev ? (unsigned*)(rgba8_dev + (size_t)i * rgba8_stride) : nullptr;
         float* rgb = rgb_dev ? (float*)((char*)rgb_dev + (size_t)i * rgb_stride) : nullptr;
-        if (int rc = launch_trace(c, kp, tiny ? &T : nullptr, S, F, f->width, rows, rgba, rgb, c->d_stats, fs))
+        if (int rc = launch_trace(c, P.kp, P.tiny ? &P.T : nullptr, P.S, P.F, f->width, rows, rgba, rgb, c->d_stats, fs))
             return rc;
-        if (tmode == 2)
+        if (P.tmode == 2)
             if (int rc = tiny_masks_stored(c, fs)) return rc;
     }
     // Join: st continues after every frame.
@@ -3102,10 +3164,7 @@ RT_EXPORT int rt_render_sequence_async(rt_ctx* c, const rt_frame* frames, int32_
             HIP_TRY(c, hipStreamWaitEvent(st, c->seq_join[j], 0));
         }
     }
-    if (capturing)
-        c->captured = true;
-    else if (n > 0)
-        note_async(c, st);
+    if (capturing || n > 0) enqueued(c, st, capturing, nullptr);  // (a slot's buffer is rebuilt in every replay)
     return RT_OK;
 }
 
@@ -3116,9 +3175,8 @@ RT_EXPORT int rt_prepare_camera(rt_ctx* c, const rt_frame* f)
     if (int rc = check_uploaded(c, "rt_prepare_camera")) return rc;
     if (int rc = check_frame(c, f)) return rc;
     if (int rc = sync_begin(c)) return rc;
-    const int depth = reachable_depth(c, f);
-    const bool cb_want = cam_lists(c, depth, lbuf_on(c)) && c->n_tri > 0 && c->opt_camera_buffer && cb_frame_ok(f);
-    if (int rc = prepare_state(c, f, c->stream, true, false, cb_want)) return rc;
+    const bool cb_want = cb_wanted(c, f, reachable_depth(c, f), lbuf_on(c));
+    if (int rc = prepare_state(c, c->cam, f, c->stream, true, false, cb_want)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     settled(c);
     return RT_OK;
@@ -3265,12 +3323,12 @@ static int launch_aov(rt_ctx* c, const rt_frame* f, const rt_aov& dev, hipStream
     if (!sync_path)
         if (int rc = stream_capturing(c, st, &capturing)) return rc;
     const bool wave0 = c->n_tri == 0 || tiny_ok(c, 0, lbuf_on(c));
-    const bool cb_want = !wave0 && c->opt_camera_buffer && cb_frame_ok(f);
+    const bool cb_want = !wave0 && cb_wanted(c, f, 0, lbuf_on(c));
     const int rows = frame_rows(f);
     if (rows > 0 && !wave0) {
-        if (int rc = prepare_state(c, f, st, sync_path, capturing, cb_want)) return rc;
+        if (int rc = prepare_state(c, c->cam, f, st, sync_path, capturing, cb_want)) return rc;
     }
-    const bool cbuf = cb_want && cb_matches(c->cb, f);
+    const bool cbuf = cb_want && cb_matches(c->cam.cb, f);
     Facts fa;
     fa.aov = true;
     fa.n_tri = c->n_tri;
@@ -3278,7 +3336,7 @@ static int launch_aov(rt_ctx* c, const rt_frame* f, const rt_aov& dev, hipStream
     fa.cbuf = cbuf;
     const Variant v = select_variant(fa);
     const KernelRow<1>* const row = find_row(kAovKernels, v);  // (the row exists: KernelRow)
-    SceneDev S = scene_dev(c, false, cbuf);
+    SceneDev S = scene_dev(c, c->cam, false, cbuf);
     FrameDev F;
     frame_dev(f, F);
     c->last = rt_stats{};
@@ -3294,12 +3352,7 @@ static int launch_aov(rt_ctx* c, const rt_frame* f, const rt_aov& dev, hipStream
     if (sync_path) HIP_TRY(c, hipEventRecord(c->ev0, st));
     HIP_TRY(c, hipLaunchKernel(row->k[0], grid, block, args, lds_bytes(v.flags, 0), st));
     if (sync_path) HIP_TRY(c, hipEventRecord(c->ev1, st));
-    if (capturing) {
-        c->captured = true;
-        if (cbuf) c->cb.pinned = true;
-    } else if (!sync_path) {
-        note_async(c, st);
-    }
+    if (!sync_path) enqueued(c, st, capturing, cbuf ? &c->cam.cb : nullptr);
     return RT_OK;
 }
 
@@ -3514,7 +3567,7 @@ RT_EXPORT int rt_debug_cb_info(rt_ctx* c, double* out, int n)
 {
     if (!c || !out || n < 4) return RT_E_ARG;
     if (c->cpu) return not_cpu(c);
-    rt_ctx::CamBuf& B = c->cb;
+    rt_ctx::CamBuf& B = c->cam.cb;
     if (B.timed) {
         float ms = 0.f;
         HIP_TRY(c, hipEventSynchronize(B.ev1));
@@ -3552,7 +3605,7 @@ RT_EXPORT int rt_debug_cb_verify(rt_ctx* c, unsigned long long* out)
     if (c->cpu) return not_cpu(c);
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = sync_all(c)) return rc;
-    rt_ctx::CamBuf& B = c->cb;
+    rt_ctx::CamBuf& B = c->cam.cb;
     if (!B.valid) {
         c->err = "no current camera buffer";
         return RT_E_STATE;
@@ -3570,7 +3623,7 @@ RT_EXPORT int rt_debug_cb_verify(rt_ctx* c, unsigned long long* out)
     D.cap = (unsigned)B.cap;
     D.tiles_x = B.tiles_x;
     D.tiles_y = B.ntiles / std::max(1, B.tiles_x);
-    const SceneDev S = scene_dev(c, false, true);
+    const SceneDev S = scene_dev(c, c->cam, false, true);
     unsigned h[2] = {0, 0};
     std::vector<unsigned> flags((size_t)B.ntiles);
     if (rc == RT_OK) {
@@ -3727,7 +3780,7 @@ RT_EXPORT int rt_debug_bvh_rays(rt_ctx* c, const float* rays, int n, int* out_id
         chk(hipMalloc(&d_tally, 2 * sizeof(unsigned long long)), "hipMalloc") &&
         chk(hipMemcpy(d_rays, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy") &&
         chk(hipMemset(d_tally, 0, 2 * sizeof(unsigned long long)), "hipMemset")) {
-        const SceneDev S = scene_dev(c, false, false);
+        const SceneDev S = scene_dev(c, c->cam, false, false);
         hipLaunchKernelGGL(rt_bvh_rays_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64),
                            (unsigned)(kLdsWaveBytes + kBvhLdsBytes), c->stream, S, d_rays, n, d_idx, d_t, d_tally);
         if (chk(hipGetLastError(), "rt_bvh_rays_kernel") && chk(hipStreamSynchronize(c->stream), "sync") &&
@@ -3765,7 +3818,7 @@ RT_EXPORT int rt_debug_bvh_rays_wave(rt_ctx* c, const float* rays, int n, int* o
         chk(hipMalloc(&d_idx, (size_t)n * sizeof(int)), "hipMalloc") &&
         chk(hipMalloc(&d_t, (size_t)n * sizeof(float)), "hipMalloc") &&
         chk(hipMemcpy(d_rays, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy")) {
-        const SceneDev S = scene_dev(c, false, false);
+        const SceneDev S = scene_dev(c, c->cam, false, false);
         // the shared stack, then lane 0's serial stack (one step: a row)
         const unsigned lds = (unsigned)(kWfStragCap * sizeof(int) + 64 * sizeof(int) * (size_t)c->bvh_depth);
         hipLaunchKernelGGL(rt_bvh_wave_kernel, dim3((unsigned)n), dim3(64), lds, c->stream, S, d_rays, n, d_idx, d_t);

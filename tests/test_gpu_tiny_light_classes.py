@@ -31,7 +31,7 @@ light below the ground; no class on a tile that shows only background; bits
 scene a).
 
 Staleness: another camera in between, the scene uploaded again with a light
-moved, two streams interleaved.
+moved, two streams interleaved, a sequence's four internal streams.
 """
 from __future__ import annotations
 
@@ -379,3 +379,39 @@ def test_two_streams_interleaved(oracle, tmp_path):
         for rep in range(4):
             assert bits_equal(outs[k][rep].cpu().numpy(), want), (k, rep)
     assert np.array_equal(words(c, W, H, streams[0].cuda_stream), words(c, W, H, streams[1].cuda_stream))
+
+
+def test_sequence_stores_and_reads_on_its_internal_streams(oracle, tmp_path):
+    """rt_render_sequence_async keeps the words per internal stream (four of
+    them, frame i on stream i % 4): 12 copies of one camera give every stream
+    that camera three times — computed, stored, read —, the same call again
+    reads 12 times, and 12 frames cycling through three cameras meet the
+    stored camera again only where its words still hold (a stream's other
+    cameras are new to it: computed).  Every frame bit for bit the oracle's,
+    and so is a synchronous render afterwards.  (A sequence fills no
+    rt_stats: which kernel ran is not seen here.)  Cameras: a and b of
+    test_another_camera_in_between, and one moved the other way."""
+    torch = pytest.importorskip("torch")
+    path = write(tmp_path, "a_box", text("a_box"))
+    s = rt_amd.Scene(path, W, H, 0)
+    cams = [s.frame, s.frame.copy(), s.frame.copy()]
+    cams[1].cam_pos[0] -= 35.0
+    cams[1].cam_pos[2] += 20.0
+    cams[2].cam_pos[0] += 35.0
+    cams[2].cam_pos[2] += 20.0
+    fr = Frames(oracle, tmp_path)
+    want = [oracle.render(path, W, H, 0)] + [fr.want(path, W, H, 0, frame=f).img for f in cams[1:]]
+    assert not any(bits_equal(want[i], want[j]) for i, j in ((0, 1), (0, 2), (1, 2)))
+    c = rt_amd.Context(0)
+    c.upload(s)
+    n = 12
+    ring = torch.zeros((n, H, W, 3), dtype=torch.float32, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    for what, order in (("a", [0] * n), ("b", [0] * n), ("c", [i % 3 for i in range(n)])):
+        ring.zero_()
+        c.render_sequence_async([cams[k] for k in order], 0, 0, ring.data_ptr(), H * W * 12, st)
+        torch.cuda.synchronize()
+        got = ring.cpu().numpy()
+        for i, k in enumerate(order):
+            assert bits_equal(got[i], want[k]), (what, i, k)
+    assert bits_equal(c.render_float(cams[0]), want[0]), "d"
