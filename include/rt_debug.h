@@ -128,6 +128,15 @@ int rt_debug_row_chunks(int width, int rows, int band_rows, int px_bytes, int ss
  * 2 dark).  RT_E_STATE where the stream holds no stored words of n tiles. */
 int rt_debug_tiny_words(rt_ctx*, void* hip_stream, unsigned* out, int n);
 
+/* The second word stored beside each of those, the tile facts (0: nothing
+ * known).  Bits 0-2: how the tile's one surface is found (1 launch-record
+ * plane slot, 2 kept triangle, 3 by the full search, 4 every lane missed);
+ * bits 3-7: that slot or triangle position; bits 8 + 2 l and 9 + 2 l, l < 6:
+ * light l's pass changed no lane's colour / every shaded lane faces light l;
+ * bits 20-31: the surface's file index + 1 (0 unknown).  Same arguments and
+ * errors as rt_debug_tiny_words. */
+int rt_debug_tiny_facts(rt_ctx*, void* hip_stream, unsigned* out, int n);
+
 #ifdef RT_PROF
 /* Only in a library built with -DRT_PROF (tools/prof_sections.py,
  * tools/prof_tiles.py): per-section shader-clock totals and event counts

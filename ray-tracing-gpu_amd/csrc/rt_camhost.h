@@ -316,7 +316,8 @@ static const TinyCam& tiny_prepare(rt_ctx* c, const rt_frame* f)
 // The storing frame (mode 2) also writes each tile's light classes into the
 // word's bits from 20 up (rt_cull.h), which the reading frames (mode 0) use to
 // skip shadow passes; they live and die with the masks: the same key, the
-// same buffer, dropped by the same upload.
+// same buffer, dropped by the same upload.  So do the tile facts, the second
+// word of each tile's 8-byte record (rt_cull.h TileRec, tile_facts_pack).
 // Buffers are found by the stream's handle, which a destroyed stream's
 // successor may reuse: the storing kernel is followed by an event
 // (tiny_masks_stored) that a reader waits for while it has not passed.  At
@@ -369,7 +370,7 @@ static int tiny_masks(rt_ctx* c, const rt_frame* f, hipStream_t st, bool capturi
         b->d = nullptr;
         b->cap = 0;
         b->valid = false;
-        HIP_TRY(c, hipMalloc((void**)&b->d, nt * sizeof(unsigned)));
+        HIP_TRY(c, hipMalloc((void**)&b->d, nt * sizeof(TileRec)));
         b->cap = nt;
     }
     std::memcpy(b->key, key, sizeof key);

@@ -478,7 +478,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     F.row_begin = H.row_begin, F.row_end = H.row_end;
     F.band_rows = H.band_rows, F.band_count = H.band_count, F.band_index = H.band_index;
     int tn = H.n, masked = H.masked, tiles_x = H.tiles_x;
-    unsigned* const mask = H.mask;
+    TileRec* const mask = H.mask;
     TinyPlanes PL;
 #pragma unroll
     for (int k = 0; k < kTinyPlanes; ++k) {
@@ -501,6 +501,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
         RT_PIN4(PL.num[k], PL.idx[k], tm, masked);
     }
 
+    // the instance that reads the tile facts (rt_cull.h tile_facts_pack): the
+    // reading frames, not a counted one (its counters are the general kernels')
+    constexpr bool FACTS = !computes_mask(WAVE) && !COUNT && RT_TILE_FACTS != 0;
+    constexpr bool AHEAD = FACTS && (RT_TILE_FACTS & 32) != 0;
+    int nl0 = 0;
+    if constexpr (AHEAD) {
+        nl0 = H.n_lights;
+        RT_PIN4(nl0, tn, masked, tiles_x);
+    }
+
     const int lane = threadIdx.x & 63;
     const int bx = (int)blockIdx.x, by = (int)blockIdx.y;  // hardware order (tile_of_block: small lists)
     const int px = bx * 8 + (lane & 7);
@@ -516,8 +526,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     // the full frame (the masks hold for its lanes' clamped pixels)
     const int tile = (py0 & 7) == 0 ? (py0 >> 3) * tiles_x + bx : -1;
     const bool tiled = masked && tile >= 0;
+    unsigned fx = 0;  // the tile facts (0: none)
     if constexpr (!computes_mask(WAVE))
-        if (tiled) tm = mask[tile];  // wave-uniform (scalar) load, waited for at the triangles
+        if (tiled) {  // wave-uniform (scalar) load, waited for at the hit
+            if constexpr (FACTS) {
+                const TileRec w = mask[tile];
+                tm = w.word, fx = w.facts;
+            } else {
+                tm = mask[tile].word;
+            }
+        }
+    // (RT_TILE_FACTS 32) the first light's hot half with the tile's record:
+    // it depends on nothing the kernel computes
+    float4 la0 = make_float4(0.f, 0.f, 0.f, 0.f), la1 = la0;
+    if constexpr (AHEAD)
+        if (nl0 > 0) la0 = H.lrec[0], la1 = H.lrec[1];
     TinyLane tl;
     if constexpr (computes_mask(WAVE)) tl = tiny_lane_load(tn, L.rec);  // the mask's records, in flight under set-up
     const int py = py0 + (lane >> 3);
@@ -563,28 +586,126 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
         if constexpr (CLS == 1) cls = tm >> kTinyClassShift;
         tm &= (1u << kTinyClassShift) - 1u;
     }
-    const int idx = closest_hit_camera_tiny(S, PL, L.rec, tm, O, D, t, cnt);
-    RT_MARK(cnt, 1);
-    // Lanes that miss (or lie outside the frame) stay in step through the
-    // shading so the wave stays whole.
-    const bool hit = idx >= 0;
-    if (__any(hit & valid)) {
-        const int sidx = hit ? idx : 0;
-        // A tile usually sees one surface: then its normal and material
-        // records come by scalar (broadcast) loads instead of a per-lane gather.
-        const int s0 = __builtin_amdgcn_readfirstlane(sidx);
-        Vec3 N;
-        Mat m;
-        if (__all(sidx == s0)) {
-            m = load_mat(S, s0);
-            N = hit_normal(S, s0, O, D, t);
-        } else {
-            m = load_mat(S, sidx);
-            N = hit_normal(S, sidx, O, D, t);
+    unsigned lf = 0;  // the lights' facts (rt_cull.h kFactLightShift), two bits each
+    if constexpr (!FACTS) {
+        const int idx = closest_hit_camera_tiny(S, PL, L.rec, tm, O, D, t, cnt);
+        RT_MARK(cnt, 1);
+        // Lanes that miss (or lie outside the frame) stay in step through the
+        // shading so the wave stays whole.
+        const bool hit = idx >= 0;
+        if constexpr (CLS == 2) {
+            // the storing frame: what the search found, for the later frames
+            const int f0 = __builtin_amdgcn_readfirstlane(idx);
+            if (!__any(hit)) {
+                fx = tile_facts_pack(kFactMiss, 0, 0, 0);
+            } else if (__all(hit & (idx == f0)) && tile_facts_surf_field(f0) != 0) {
+                unsigned k = kFactSearch, sl = 0;
+#pragma unroll
+                for (int q = 0; q < kTinyPlanes; ++q)
+                    if (q < S.n_plane && PL.idx[q] == f0) k = kFactPlane, sl = (unsigned)q;
+                for (unsigned mm = tm; mm && k == kFactSearch;) {
+                    const int j = (int)__builtin_ctz(mm);
+                    mm &= mm - 1u;
+                    if (__float_as_int(L.rec[8 * j + 7].y) == f0) k = kFactTri, sl = (unsigned)j;
+                }
+                fx = tile_facts_pack(k, sl, 0, tile_facts_surf_field(f0));
+            }
         }
-        const Vec3 P = O + t * D;
-        const Color cl = shade_local_tiny<CLS>(S, PL, H.lrec, m, P, N, D, cnt, hit & valid, cls);
-        c = hit ? cl : bg;
+        if (__any(hit & valid)) {
+            const int sidx = hit ? idx : 0;
+            // A tile usually sees one surface: then its normal and material
+            // records come by scalar (broadcast) loads instead of a per-lane gather.
+            const int s0 = __builtin_amdgcn_readfirstlane(sidx);
+            Vec3 N;
+            Mat m;
+            if (__all(sidx == s0)) {
+                m = load_mat(S, s0);
+                N = hit_normal(S, s0, O, D, t);
+            } else {
+                m = load_mat(S, sidx);
+                N = hit_normal(S, sidx, O, D, t);
+            }
+            const Vec3 P = O + t * D;
+            const Color cl = shade_local_tiny<CLS>(S, PL, H.lrec, m, P, N, D, cnt, hit & valid, cls, lf, la0, la1);
+            c = hit ? cl : bg;
+        }
+    } else {
+        // The reading frames, with the tile facts (all wave-uniform).  A tile
+        // that shows one known surface takes its material and normal by
+        // scalar loads issued here, in flight under the search (2), and tests
+        // only the primitive the storing frame found it by: the same function
+        // on the same operands, so the same t, and by determinism every lane
+        // hits it (4).  A tile every lane missed keeps the background (1).
+        static_assert(kTinyPlanes == 2, "the plane slot is picked by one select");
+        const unsigned kind = tile_facts_kind(fx), slot = tile_facts_slot(fx);
+        const int s0 = (int)tile_facts_surf(fx) - 1;
+        lf = tile_facts_lights(fx);
+        if constexpr ((RT_TILE_FACTS & 8) != 0) {
+            // a no-op pass: class 3, both bits of the light's class
+            static_assert(kTinyClassLights == 6, "0x555: the no-op bit of each light");
+            const unsigned np = lf & 0x555u;
+            cls |= np | np << 1;
+        }
+        const bool miss = (RT_TILE_FACTS & 1) != 0 && kind == kFactMiss;
+        const bool known =
+            (RT_TILE_FACTS & 6) != 0 && s0 >= 0 && (kind == kFactPlane || kind == kFactTri || kind == kFactSearch);
+        Mat m{};
+        Vec3 N = make3(0.f, 0.f, 0.f);
+        bool have_n = false;
+        if constexpr ((RT_TILE_FACTS & 2) != 0) {
+            if (known) {
+                m = load_mat(S, s0);
+                const float4* g = S.geom + 4 * s0;
+                if (kind == kFactPlane) {
+                    const float4 a = g[0];
+                    N = make3(a.y, a.z, a.w);
+                    have_n = true;
+                } else if (kind == kFactTri) {
+                    const float4 c2 = g[2], d2 = g[3];
+                    N = make3(c2.z, c2.w, d2.x);
+                    have_n = true;
+                }
+            }
+        }
+        int idx = -1;
+        t = -1.0f;
+        bool hit = false, lit = false;
+        if ((RT_TILE_FACTS & 4) != 0 && known && kind != kFactSearch) {
+            if (kind == kFactPlane) {
+                // closest_hit_camera_tiny's plane slot, alone
+                const float4 a = slot ? PL.a[1] : PL.a[0];
+                const float num = slot ? PL.num[1] : PL.num[0];
+                t = -num / dot(make3(a.x, a.y, a.z), D);
+            } else {
+                const float4* r = L.rec + 8 * slot + 4;
+                camera_tri<true>(r[0], r[1], r[2], r[3], D, t, idx, cnt);
+            }
+            hit = lit = true;
+        } else if (!miss) {
+            idx = closest_hit_camera_tiny(S, PL, L.rec, tm, O, D, t, cnt);
+            hit = idx >= 0;
+            lit = __any(hit & valid);
+        }
+        RT_MARK(cnt, 1);
+        if (lit) {
+            if (known) {
+                if constexpr ((RT_TILE_FACTS & 2) == 0) m = load_mat(S, s0);
+                if (!have_n) N = hit_normal(S, s0, O, D, t);
+            } else {
+                const int sidx = hit ? idx : 0;
+                const int b0 = __builtin_amdgcn_readfirstlane(sidx);
+                if (__all(sidx == b0)) {
+                    m = load_mat(S, b0);
+                    N = hit_normal(S, b0, O, D, t);
+                } else {
+                    m = load_mat(S, sidx);
+                    N = hit_normal(S, sidx, O, D, t);
+                }
+            }
+            const Vec3 P = O + t * D;
+            const Color cl = shade_local_tiny<CLS>(S, PL, H.lrec, m, P, N, D, cnt, hit & valid, cls, lf, la0, la1);
+            c = hit ? cl : bg;
+        }
     }
     if (valid) {
         const size_t o = (size_t)ly * F.width + px;
@@ -603,9 +724,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     // (kMaskStore), stored last: at the top of the kernel the store's
     // completion held up the loads behind it (A/B: C2 -2.8%, C4 -2.5%).
     // Above the mask's 20 bits, the light classes the shading gathered (0
-    // where the tile was not shaded).
+    // where the tile was not shaded); beside the word, the tile facts.
     if constexpr (stores_mask(WAVE))
-        if (lane == 0 && tiled) mask[tile] = tmask | cls << kTinyClassShift;
+        if (lane == 0 && tiled) mask[tile] = TileRec{tmask | cls << kTinyClassShift, fx | lf << kFactLightShift};
     tile_prof_flush(cnt);
     if (COUNT && (H.flags & RT_FLAG_STATS)) tile_tally(cnt, H.stats, true);  // (every lane runs)
 }
@@ -853,7 +974,7 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
     bool opt_launch_camera = true;  // RT_OPT_LAUNCH_CAMERA
     struct MaskBuf {
         hipStream_t stream = nullptr;
-        unsigned* d = nullptr;
+        TileRec* d = nullptr;  // one record per tile: the word and the tile facts (rt_cull.h)
         size_t cap = 0;
         float key[30] = {};   // the camera whose masks d holds (valid)
         bool valid = false;
@@ -3643,7 +3764,7 @@ RT_EXPORT int rt_debug_cb_verify(rt_ctx* c, unsigned long long* out)
 // Diagnostic (include/rt_debug.h): the tile words (rt_cull.h: mask and light
 // classes) a launch-camera render stored for `stream` (tiny_masks; NULL: the
 // synchronous renders' stream), the first n of them.  Synchronous.
-RT_EXPORT int rt_debug_tiny_words(rt_ctx* c, void* stream, unsigned* out, int n)
+static int tiny_records_read(rt_ctx* c, void* stream, unsigned* out, int n, bool facts)
 {
     if (!c || !out || n < 0) return RT_E_ARG;
     if (c->cpu) return not_cpu(c);
@@ -3652,11 +3773,23 @@ RT_EXPORT int rt_debug_tiny_words(rt_ctx* c, void* stream, unsigned* out, int n)
     const hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     for (const auto& q : c->tiny_masks)
         if (q.stream == st && q.valid && q.d && (size_t)n <= q.cap) {
-            HIP_TRY(c, hipMemcpy(out, q.d, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));
+            std::vector<TileRec> h((size_t)n);
+            HIP_TRY(c, hipMemcpy(h.data(), q.d, (size_t)n * sizeof(TileRec), hipMemcpyDeviceToHost));
+            for (int i = 0; i < n; ++i) out[i] = facts ? h[(size_t)i].facts : h[(size_t)i].word;
             return RT_OK;
         }
     c->err = "no stored tile words of that size for the stream";
     return RT_E_STATE;
+}
+RT_EXPORT int rt_debug_tiny_words(rt_ctx* c, void* stream, unsigned* out, int n)
+{
+    return tiny_records_read(c, stream, out, n, false);
+}
+// Diagnostic (include/rt_debug.h): the same records' second word, the tile
+// facts (rt_cull.h tile_facts_pack).
+RT_EXPORT int rt_debug_tiny_facts(rt_ctx* c, void* stream, unsigned* out, int n)
+{
+    return tiny_records_read(c, stream, out, n, true);
 }
 
 // Diagnostic (include/rt_debug.h): the last rt_upload_scene's host wall

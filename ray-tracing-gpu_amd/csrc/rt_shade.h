@@ -1137,18 +1137,56 @@ __device__ __forceinline__ void shadow_opaque_tiny(const SceneDev& S, const Tiny
 // dark sets every lane's.  Same camera, frame and scene, so the same P, N
 // and gate lane for lane: exact by determinism.  Class 0, and every light
 // from kTinyClassLights up, runs the pass.
+// lf: the tile facts' light bits (rt_cull.h kFactNoop, kFactGated), two per
+// light as the classes.  CLS 2 gathers them: no-op by comparing the colour's
+// bits before and after the pass in every active lane (so signed zeros,
+// non-finite terms and the Phong term need no argument), all gated from the
+// gate.  CLS 1 skips a no-op pass whole (RT_TILE_FACTS 8: the caller has
+// or-ed the no-op bit into both bits of the light's class, class 3, so the
+// pass carries no state beside `rest`), takes the gate of an all-gated lit
+// pass as given (16: the clamped and missing lanes then run add_light too,
+// their colour is dropped), reads the record's hot half [pos I] [rgb dcov] one
+// light ahead — n0, n1: the first light's, loaded by the caller — (32) and
+// the cold half [m0] [rg] only inside the shadow pass's branch (32, 64).
 template <int CLS>
 __device__ __forceinline__ Color shade_local_tiny(const SceneDev& S, const TinyPlanes& PL, const float4* lrec,
                                                   const Mat& m, const Vec3 P, const Vec3 N, const Vec3 D,
-                                                  Counters& cnt, bool active, unsigned& cls)
+                                                  Counters& cnt, bool active, unsigned& cls, unsigned& lf, float4 n0,
+                                                  float4 n1)
 {
+    constexpr bool AHEAD = CLS == 1 && (RT_TILE_FACTS & 32) != 0;
+    constexpr bool COLD = CLS == 1 && (RT_TILE_FACTS & (32 | 64)) != 0;
+    constexpr bool SKIP = CLS == 1 && (RT_TILE_FACTS & 8) != 0;
+    constexpr bool GATED = CLS == 1 && (RT_TILE_FACTS & 16) != 0;
     Color res = m.color * m.ka;
     const float4* r = lrec;  // the light's record (a running pointer)
     unsigned rest = cls;  // CLS 1: this and the later lights' classes
+    [[maybe_unused]] unsigned frest = lf;  // and facts (GATED)
     for (int li = 0; li < S.n_lights; ++li, r += kLightRec) {
-        const float4 l0 = r[0], l1 = r[1], m0 = r[2], rg = r[3];
+        float4 l0, l1, m0, rg;
+        if constexpr (AHEAD) {
+            l0 = n0, l1 = n1;
+            const float4* nx = li + 1 < S.n_lights ? r + kLightRec : r;  // (the last light: its own again)
+            n0 = nx[0], n1 = nx[1];
+        }
+        [[maybe_unused]] unsigned k = 0;  // CLS 1: the light's class, wave-uniform
+        if constexpr (CLS == 1) {
+            k = rest & 3u;
+            rest >>= 2;
+        }
+        [[maybe_unused]] unsigned fk = 0;
+        if constexpr (GATED) {
+            fk = frest & 3u;
+            frest >>= 2;
+        }
+        if constexpr (SKIP)
+            if (k == 3u) continue;
+        if constexpr (!AHEAD) l0 = r[0], l1 = r[1];
+        if constexpr (!COLD) m0 = r[2], rg = r[3];
         const Vec3 Lr = make3(l0.x, l0.y, l0.z) - P;
-        const bool gate = active & (dot(Lr, N) > 0);  // Scene.cpp:1756, unnormalised
+        bool gate;
+        if constexpr (GATED) gate = ((fk & kFactGated) != 0 && k == 1u) ? true : active & (dot(Lr, N) > 0);
+        else gate = active & (dot(Lr, N) > 0);  // Scene.cpp:1756, unnormalised
         float dist, inv;
         sqrt_recip_w(Lr.x * Lr.x + Lr.y * Lr.y + Lr.z * Lr.z, dist, inv);
         const Vec3 L = Lr * inv;
@@ -1166,14 +1204,15 @@ __device__ __forceinline__ Color shade_local_tiny(const SceneDev& S, const TinyP
         asm("" : "+s"(T.n_plane_opaque), "+s"(T.n_quad_opaque), "+s"(T.n_translucent), "+s"(T.n_tri_opaque)
             : "s"(li));
         if constexpr (CLS == 1) {
-            const unsigned k = rest & 3u;  // wave-uniform
-            rest >>= 2;
             occ |= k == 2u;
             // the pass out of line (most tiles have a class): without the
             // hint the instance holds 26 scalars in vector lanes, with the
             // result set in an else branch 41, this way 15 (the parent 18;
             // tools/isa_classes.py lane_spill)
-            if (__builtin_expect(k == 0, 0)) shadow_opaque_tiny(T, PL, m0, rg, l1.w, li, P, L, dist, occ, cnt);
+            if (__builtin_expect(k == 0, 0)) {
+                if constexpr (COLD) m0 = r[2], rg = r[3];
+                shadow_opaque_tiny(T, PL, m0, rg, l1.w, li, P, L, dist, occ, cnt);
+            }
         } else {
             shadow_opaque_tiny(T, PL, m0, rg, l1.w, li, P, L, dist, occ, cnt);
         }
@@ -1183,6 +1222,7 @@ __device__ __forceinline__ Color shade_local_tiny(const SceneDev& S, const TinyP
             if (li < kTinyClassLights) cls |= k << (2 * li);
         }
         RT_MARK(cnt, 7);
+        [[maybe_unused]] const Color before = res;
         if (gate) {
             Color F{0.0f, 0.0f, 0.0f};
             if (!occ) {  // translucent surfaces, file order
@@ -1193,6 +1233,13 @@ __device__ __forceinline__ Color shade_local_tiny(const SceneDev& S, const TinyP
                 }
             }
             add_light(res, m, l0, l1, N, L, D, F);  // reads l1's colour only
+        }
+        if constexpr (CLS == 2) {
+            const bool same = (__float_as_uint(res.r) == __float_as_uint(before.r)) &
+                              (__float_as_uint(res.g) == __float_as_uint(before.g)) &
+                              (__float_as_uint(res.b) == __float_as_uint(before.b));
+            const unsigned k = (__all(!active | same) ? kFactNoop : 0u) | (__all(!active | gate) ? kFactGated : 0u);
+            if (li < kTinyClassLights) lf |= k << (2 * li);
         }
         RT_MARK(cnt, 5);
     }
