@@ -137,6 +137,14 @@ int rt_debug_tiny_words(rt_ctx*, void* hip_stream, unsigned* out, int n);
  * errors as rt_debug_tiny_words. */
 int rt_debug_tiny_facts(rt_ctx*, void* hip_stream, unsigned* out, int n);
 
+/* The lean records stored beside them, 16 dwords per tile into
+ * out[16 * n_tiles]: [0] the word, [1] the facts — on a lean tile with kind 5
+ * (for 1, a plane slot) or 6 (for 2, a kept triangle) —, then as floats
+ * [2-4] the plane slot's normal and [5] its n . camera + cst (a plane tile),
+ * [6-8] the hit normal, [9-11] the colour, [12-15] Ka Kd Ks shininess; zeros
+ * from [2] on where the tile is not lean.  Same errors as rt_debug_tiny_words. */
+int rt_debug_tiny_lean(rt_ctx*, void* hip_stream, unsigned* out, int n_tiles);
+
 #ifdef RT_PROF
 /* Only in a library built with -DRT_PROF (tools/prof_sections.py,
  * tools/prof_tiles.py): per-section shader-clock totals and event counts

@@ -357,6 +357,7 @@ static int tiny_masks(rt_ctx* c, const rt_frame* f, hipStream_t st, bool capturi
             else return hip_fail(c, q, "hipEventQuery");
         }
         T.mask = b->d;
+        T.lean = b->lean;
         *mode = 0;
         return RT_OK;
     }
@@ -368,15 +369,20 @@ static int tiny_masks(rt_ctx* c, const rt_frame* f, hipStream_t st, bool capturi
     if (b->cap < nt) {  // the camera's second frame: compute and store
         if (b->d) free_later(c, b->d);
         b->d = nullptr;
+        b->lean = nullptr;
         b->cap = 0;
         b->valid = false;
-        HIP_TRY(c, hipMalloc((void**)&b->d, nt * sizeof(TileRec)));
+        // one allocation, two arrays: the TileRecs, then (64-byte aligned) the lean records
+        const size_t lean_off = (nt * sizeof(TileRec) + alignof(LeanRec) - 1) / alignof(LeanRec) * alignof(LeanRec);
+        HIP_TRY(c, hipMalloc((void**)&b->d, lean_off + nt * sizeof(LeanRec)));
+        b->lean = reinterpret_cast<LeanRec*>(reinterpret_cast<char*>(b->d) + lean_off);
         b->cap = nt;
     }
     std::memcpy(b->key, key, sizeof key);
     b->valid = true;
     b->pend_valid = false;
     T.mask = b->d;
+    T.lean = b->lean;
     *mode = 2;
     return RT_OK;
 }

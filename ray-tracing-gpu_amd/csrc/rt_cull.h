@@ -10,6 +10,7 @@
 
 #include "rt_dims.h"
 #include "rt_primitives.h"
+#include "rt_tile.h"
 #include "rt_variant.h"
 
 #pragma clang fp contract(off)
@@ -420,69 +421,7 @@ __device__ __forceinline__ int closest_hit_camera_list(const SceneDev& S, int ti
 // computes what that frame's lane computed and the pass would end the same:
 // it is skipped (rt_shade.h shade_local_tiny).  Counted renders ignore the
 // classes.
-constexpr int kTinyMax = 20;
-constexpr int kTinyClassShift = 20, kTinyClassLights = 6;
-static_assert(kTinyMax <= 20, "the tile word's bits from 20 up are the light classes");
-static_assert(kTinyMax <= kTinyClassShift && kTinyClassShift + 2 * kTinyClassLights <= 32, "the tile word is 32 bits");
-
-// The tile's second word, the tile facts: stored beside the word above (one
-// 8-byte record per tile, TileRec) by the same frame, read by the same later
-// frames, exact by the same determinism.  0: nothing is known.
-//   bits 0-2   kind: how the tile's one surface is found (kFact*)
-//   bits 3-7   the launch record's plane slot (kFactPlane) or the kept
-//              triangle's position in the camera records (kFactTri)
-//   bits 8-19  per light li < kTinyClassLights two bits: 8 + 2 li no-op (the
-//              pass left the colour bit-identical in every active lane),
-//              9 + 2 li all gated (every active lane passed dot(Lr, N) > 0)
-//   bits 20-31 surf + 1, the file index every lane's winner has (0: unknown,
-//              or an index past the field)
-// Kinds: every lane of the wave (clamped lanes included: each repeats a pixel
-// of the tile) missed, or every lane's winner is the one surface `surf`.
-constexpr unsigned kFactNone = 0, kFactPlane = 1, kFactTri = 2, kFactSearch = 3, kFactMiss = 4;
-constexpr int kFactKindBits = 3, kFactSlotShift = 3, kFactSlotBits = 5, kFactLightShift = 8, kFactSurfShift = 20;
-constexpr unsigned kFactSurfMax = (1u << (32 - kFactSurfShift)) - 2u;  // the largest index the field holds
-constexpr unsigned kFactNoop = 1, kFactGated = 2;  // a light's two bits
-static_assert(kFactMiss < (1u << kFactKindBits), "the kind's field");
-static_assert(kTinyMax <= (1 << kFactSlotBits), "a kept triangle's position fits the slot field");
-static_assert(kFactSlotShift == kFactKindBits && kFactLightShift == kFactSlotShift + kFactSlotBits &&
-                  kFactSurfShift == kFactLightShift + 2 * kTinyClassLights && kFactSurfShift < 32,
-              "the tile facts are 32 bits, fields back to back");
-constexpr unsigned tile_facts_pack(unsigned kind, unsigned slot, unsigned lights, unsigned surf_plus_1)
-{
-    return kind | slot << kFactSlotShift | lights << kFactLightShift | surf_plus_1 << kFactSurfShift;
-}
-constexpr unsigned tile_facts_kind(unsigned w) { return w & ((1u << kFactKindBits) - 1u); }
-constexpr unsigned tile_facts_slot(unsigned w) { return (w >> kFactSlotShift) & ((1u << kFactSlotBits) - 1u); }
-constexpr unsigned tile_facts_lights(unsigned w)
-{
-    return (w >> kFactLightShift) & ((1u << (2 * kTinyClassLights)) - 1u);
-}
-constexpr unsigned tile_facts_surf(unsigned w) { return w >> kFactSurfShift; }  // surf + 1
-// the field of a file index: surf + 1, 0 where it does not fit
-constexpr unsigned tile_facts_surf_field(int surf)
-{
-    return surf >= 0 && (unsigned)surf <= kFactSurfMax ? (unsigned)surf + 1u : 0u;
-}
-static_assert(tile_facts_kind(tile_facts_pack(kFactMiss, 31, 0xFFF, 0xFFF)) == kFactMiss &&
-                  tile_facts_slot(tile_facts_pack(kFactTri, 19, 0, 0)) == 19 &&
-                  tile_facts_lights(tile_facts_pack(0, 0, 0xABC, 0)) == 0xABC &&
-                  tile_facts_surf(tile_facts_pack(kFactSearch, 0, 0, 4095)) == 4095 &&
-                  tile_facts_surf_field((int)kFactSurfMax) == 4095 && tile_facts_surf_field((int)kFactSurfMax + 1) == 0,
-              "pack and unpack agree");
-// What the reading instance does with the facts, one bit per part (a build
-// option for tools/ab_variants.py; profiles/r13/tile_facts/README.md):
-//   1 miss tile: store the background   2 known surface: its records loaded early
-//   4 known primitive: only it is tested   8 no-op pass skipped
-//   16 all-gated pass without the gate's dot product   32 the light record's
-//   hot half one light ahead, its cold half inside the shadow pass's branch
-//   64 only the cold half inside that branch
-#ifndef RT_TILE_FACTS
-#define RT_TILE_FACTS (1 | 4 | 8 | 64)
-#endif
-struct alignas(8) TileRec {
-    unsigned word, facts;
-};
-static_assert(sizeof(TileRec) == 8, "one tile's record: two words, one 8-byte scalar load");
+// (The words' constants, TileRec and the lean record: rt_tile.h.)
 
 struct TinyCam {
     int n;       // listed triangles (never-hit ones left out)
@@ -490,6 +429,7 @@ struct TinyCam {
     int tiles_x, tiles_y;
     float cosW, sinW, chord, pad;  // the tile cone's width (wbound), as wave_cone would hold it
     TileRec* mask;                 // per tile of the full frame: word bit j = keep triangle j, and the facts
+    LeanRec* lean;                 // beside it, per tile: the lean records (rt_tile.h; the same buffer)
     // per triangle, nearest first: the mask planes (cone, edge 0, edge 1,
     // edge 2 paired as TinyLane holds them), the tricam record [0] [1] [2]
     // [3 = tq, file index, dmin, unused]
@@ -553,16 +493,33 @@ struct TinyHead {
     int n_lights, n_tri, n_tri_opaque, n_plane_opaque;
     int n_quad, n_quad_opaque, n_translucent, shadow_split;
     int flags;  // read at the end of a counting launch only
+    // ---- in what was the record's tail padding, so that no field above moved
+    LeanRec* lean;  // TinyCam's lean records (the reading frames' instance only)
 };
 struct TinyLaunch {
     TinyHead h;
     // per triangle, nearest first: TinyCam's records
     float4 rec[8 * kTinyMax];
+#if (RT_TILE_LEAN & 4) != 0
+    // behind everything the other instances read: the lights' hot halves for
+    // the lean path (rt_tile.h lean_lights_fill)
+    float lights[kTinyClassLights][kLeanLightFloats];
+#endif
 };
+static_assert(offsetof(TinyHead, mask) == 0x80 && offsetof(TinyHead, planes) == 0xe8 &&
+                  offsetof(TinyHead, n_lights) == 0x130 && offsetof(TinyHead, flags) == 0x150 &&
+                  offsetof(TinyHead, lean) == 0x158 && sizeof(TinyHead) == 0x160 && offsetof(TinyLaunch, rec) == 0x160,
+              "the launch record's offsets, which the instances that do not read the lean record keep");
+#if (RT_TILE_LEAN & 4) != 0
+static_assert(offsetof(TinyLaunch, lights) == sizeof(TinyHead) + sizeof(float4) * 8 * kTinyMax,
+              "the lights by value come last");
+#endif
+static_assert(sizeof(TinyLaunch) <= 4096, "the launch record fits the kernel-argument segment");
 // The header of one launch (host side; rt_trace_tiny unpacks it): the
 // frame's, the scene's and the camera records' wave-uniform values.
 // h_plane: the host copy of plane[] ([n cst] [file index 0 0 0] per plane);
-// lrec: the light records' set the launch shades with.
+// lrec: the light records' set the launch shades with.  (TinyLaunch::lights
+// is filled by the caller, from the host copy of the records.)
 inline void tiny_head_fill(TinyHead& H, const FrameDev& F, const SceneDev& S, const TinyCam& T, const float* h_plane,
                            const float4* lrec, unsigned* rgba, float* rgbf, StatsDev* stats)
 {
@@ -577,7 +534,7 @@ inline void tiny_head_fill(TinyHead& H, const FrameDev& F, const SceneDev& S, co
     H.row_begin = F.row_begin, H.row_end = F.row_end;
     H.band_rows = F.band_rows, H.band_count = F.band_count, H.band_index = F.band_index;
     H.flags = F.flags;
-    H.n = T.n, H.masked = T.masked, H.mask = T.mask, H.tiles_x = T.tiles_x;
+    H.n = T.n, H.masked = T.masked, H.mask = T.mask, H.lean = T.lean, H.tiles_x = T.tiles_x;
     H.tm_all = T.n >= 32 ? ~0u : (1u << T.n) - 1u;
     H.n_plane = S.n_plane;
     // the planes' camera-ray constants, hit_plane's n . O + cst in float

@@ -446,6 +446,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
 // wave-uniform load from the scalar cache).
 #define RT_PIN4(a, b, c, d) asm("" : "+s"(a), "+s"(b), "+s"(c), "+s"(d))
 
+// rt_trace_tiny's pixel store, for its lean path (the general path keeps its
+// own copy of these lines: its instances' code is to stay what it was
+// measured as).
+__device__ __forceinline__ void tiny_store_px(float* rgbf, unsigned* rgba, size_t o, const Color c)
+{
+    if (rgbf) {
+        rgbf[3 * o] = c.r;
+        rgbf[3 * o + 1] = c.g;
+        rgbf[3 * o + 2] = c.b;
+    }
+    // nontemporal (streaming) stores, as every small-list kernel (trace_tile)
+    if (rgba)
+        __builtin_nontemporal_store(unorm8(c.r) | (unorm8(c.g) << 8) | (unorm8(c.b) << 16) | 0xFF000000u, rgba + o);
+}
+
 // Tiny scenes (kTiny): one 8 x 8 tile of a depth-0 frame whose
 // wave-uniform inputs all come with the launch (rt_cull.h TinyLaunch, one
 // by-value argument read from the kernel-argument segment by scalar loads).
@@ -488,22 +503,51 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     }
     int n_plane = H.n_plane;
     unsigned tm = H.tm_all;  // no masks: every listed triangle
+    // the instance that reads the tile facts (rt_cull.h tile_facts_pack): the
+    // reading frames, not a counted one (its counters are the general kernels')
+    constexpr bool FACTS = !computes_mask(WAVE) && !COUNT && RT_TILE_FACTS != 0;
+    // the lean record (rt_tile.h LeanRec, RT_TILE_LEAN): the storing instances
+    // write it, the FACTS instance reads it in place of the TileRec and takes
+    // a lean tile down a path of its own (below, behind the ray set-up)
+    constexpr bool LEAN_WR = stores_mask(WAVE) && (RT_TILE_LEAN & 1) != 0;
+    constexpr bool LEAN_RD = FACTS && (RT_TILE_LEAN & 2) != 0;
+    constexpr bool LEAN_BV = LEAN_RD && (RT_TILE_LEAN & 4) != 0;
+    // its records as 16-dword vectors in the global address space: the
+    // pointer's halves pass through scalar registers with the header's first
+    // batch (the first pin: one wait for all of it), and a pointer rebuilt
+    // from them needs the address space named to be read by a scalar load
+    typedef unsigned LeanWords __attribute__((ext_vector_type(16)));
+    typedef const __attribute__((address_space(1))) LeanWords* LeanPtr;
+#if (RT_TILE_LEAN & 4) != 0
+    [[maybe_unused]] const float (*const lean_lv)[kLeanLightFloats] = L.lights;
+#else
+    [[maybe_unused]] const float (*const lean_lv)[kLeanLightFloats] = nullptr;
+#endif
+    [[maybe_unused]] LeanPtr lean = nullptr;
+    [[maybe_unused]] int lean_nl = 0;
+    if constexpr (LEAN_RD) {
+        lean_nl = H.n_lights;
+        unsigned lo = (unsigned)(size_t)H.lean, hi = (unsigned)((size_t)H.lean >> 32);
+        RT_PIN4(lo, hi, lean_nl, tiles_x);
+        lean = (LeanPtr)((size_t)lo | (size_t)hi << 32);
+    }
     RT_PIN4(F.cam[0], F.cam[1], F.cam[2], F.width);
 #pragma unroll
     for (int i = 0; i < 4; ++i) RT_PIN4(F.orient[4 * i], F.orient[4 * i + 1], F.orient[4 * i + 2], F.half_w);
     RT_PIN4(F.half_h, F.inv_w, F.inv_h, F.height);
     RT_PIN4(F.row_begin, F.row_end, F.band_rows, F.band_count);
     RT_PIN4(F.band_index, tn, masked, tiles_x);
-    RT_PIN4(n_plane, F.bg[0], F.bg[1], F.bg[2]);
+    // (the lean reader's instance leaves the planes to its general path: they
+    // are loaded where that path begins, and held by no lean tile)
+    if constexpr (!LEAN_RD) {
+        RT_PIN4(n_plane, F.bg[0], F.bg[1], F.bg[2]);
 #pragma unroll
-    for (int k = 0; k < kTinyPlanes; ++k) {
-        RT_PIN4(PL.a[k].x, PL.a[k].y, PL.a[k].z, PL.a[k].w);
-        RT_PIN4(PL.num[k], PL.idx[k], tm, masked);
+        for (int k = 0; k < kTinyPlanes; ++k) {
+            RT_PIN4(PL.a[k].x, PL.a[k].y, PL.a[k].z, PL.a[k].w);
+            RT_PIN4(PL.num[k], PL.idx[k], tm, masked);
+        }
     }
 
-    // the instance that reads the tile facts (rt_cull.h tile_facts_pack): the
-    // reading frames, not a counted one (its counters are the general kernels')
-    constexpr bool FACTS = !computes_mask(WAVE) && !COUNT && RT_TILE_FACTS != 0;
     constexpr bool AHEAD = FACTS && (RT_TILE_FACTS & 32) != 0;
     int nl0 = 0;
     if constexpr (AHEAD) {
@@ -527,9 +571,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     const int tile = (py0 & 7) == 0 ? (py0 >> 3) * tiles_x + bx : -1;
     const bool tiled = masked && tile >= 0;
     unsigned fx = 0;  // the tile facts (0: none)
+    [[maybe_unused]] LeanRec lr{};  // the tile's lean record (LEAN_RD; facts 0: not lean)
     if constexpr (!computes_mask(WAVE))
         if (tiled) {  // wave-uniform (scalar) load, waited for at the hit
-            if constexpr (FACTS) {
+            if constexpr (LEAN_RD) {
+                const LeanWords q = lean[tile];  // the TileRec's two words come with it
+                static_assert(sizeof(LeanWords) == sizeof(LeanRec), "one record, one load");
+                lr.word = q[0], lr.facts = q[1];
+                lr.pn[0] = __uint_as_float(q[2]), lr.pn[1] = __uint_as_float(q[3]), lr.pn[2] = __uint_as_float(q[4]);
+                lr.pnum = __uint_as_float(q[5]);
+                lr.nrm[0] = __uint_as_float(q[6]), lr.nrm[1] = __uint_as_float(q[7]), lr.nrm[2] = __uint_as_float(q[8]);
+                lr.color[0] = __uint_as_float(q[9]), lr.color[1] = __uint_as_float(q[10]);
+                lr.color[2] = __uint_as_float(q[11]);
+                lr.ka = __uint_as_float(q[12]), lr.kd = __uint_as_float(q[13]), lr.ks = __uint_as_float(q[14]);
+                lr.shin = __uint_as_float(q[15]);
+            } else if constexpr (FACTS) {
                 const TileRec w = mask[tile];
                 tm = w.word, fx = w.facts;
             } else {
@@ -557,6 +613,40 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     const Vec3 D = camera_dir_tiny(F, pxc, pyc);
     const Vec3 O = make3(F.cam[0], F.cam[1], F.cam[2]);
     cnt.primary = valid ? 1u : 0u;
+    // ---- a lean tile (rt_tile.h): one known surface, a class for every light.
+    // The general path's functions on the general path's operands, in its
+    // order — the record's plane, normal and material are the values it
+    // loads for the facts' surface — with no scene pointer read: the
+    // record's wait is the last one that hangs on the tile (a triangle
+    // tile's camera record comes from the launch record; the lights from the
+    // light records, or with RT_TILE_LEAN 4 from the launch record too).
+    if constexpr (LEAN_RD) {
+        // the record's first use stands behind the ray set-up: tied to D, or
+        // the compiler lifts the word's shift to the load and waits there
+        asm("" : "+s"(lr.word), "+s"(lr.facts) : "v"(D.x), "v"(D.y), "v"(D.z));
+        if (tiled) tm = lr.word, fx = lr.facts;
+        const unsigned lk = tile_facts_kind(lr.facts);
+        if (lean_kind(lk)) {
+            float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;  // the first light, in flight under the hit
+            if (lean_nl > 0) lean_light_load<LEAN_BV>(H.lrec, lean_lv, 0, a0, a1);
+            float tl_ = -1.0f;
+            if (lk == kFactLeanPlane) {
+                tl_ = -lr.pnum / dot(make3(lr.pn[0], lr.pn[1], lr.pn[2]), D);
+            } else {
+                int ti = -1;
+                const float4* r = L.rec + 8 * tile_facts_slot(lr.facts) + 4;
+                camera_tri<true>(r[0], r[1], r[2], r[3], D, tl_, ti, cnt);
+            }
+            const Mat m{{lr.color[0], lr.color[1], lr.color[2]}, lr.ka, lr.kd, lr.ks, lr.shin, 0.f, 0.f, 0.f};
+            const Vec3 N = make3(lr.nrm[0], lr.nrm[1], lr.nrm[2]);
+            const Vec3 P = O + tl_ * D;
+            const unsigned lc = lean_classes(lr.word >> kTinyClassShift, tile_facts_lights(lr.facts));
+            const Color cl = shade_lean_tiny<LEAN_BV>(H.lrec, lean_lv, lean_nl, m, P, N, D, valid, lc, a0, a1);
+            if (valid) tiny_store_px(H.rgbf, H.rgba, (size_t)ly * F.width + px, cl);
+            tile_prof_flush(cnt);
+            return;
+        }
+    }
     unsigned tmask = 0;
     if constexpr (computes_mask(WAVE)) {
         tmask = tiny_tile_mask(tn, tl, D);
@@ -587,6 +677,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
         tm &= (1u << kTinyClassShift) - 1u;
     }
     unsigned lf = 0;  // the lights' facts (rt_cull.h kFactLightShift), two bits each
+    [[maybe_unused]] Mat lean_m{};  // LEAN_WR: the shaded surface's material and normal
+    [[maybe_unused]] Vec3 lean_n = make3(0.f, 0.f, 0.f);
     if constexpr (!FACTS) {
         const int idx = closest_hit_camera_tiny(S, PL, L.rec, tm, O, D, t, cnt);
         RT_MARK(cnt, 1);
@@ -628,6 +720,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
             const Vec3 P = O + t * D;
             const Color cl = shade_local_tiny<CLS>(S, PL, H.lrec, m, P, N, D, cnt, hit & valid, cls, lf, la0, la1);
             c = hit ? cl : bg;
+            if constexpr (LEAN_WR) lean_m = m, lean_n = N;
         }
     } else {
         // The reading frames, with the tile facts (all wave-uniform).  A tile
@@ -727,6 +820,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_per_eu
     // where the tile was not shaded); beside the word, the tile facts.
     if constexpr (stores_mask(WAVE))
         if (lane == 0 && tiled) mask[tile] = TileRec{tmask | cls << kTinyClassShift, fx | lf << kFactLightShift};
+    // and its lean record (rt_tile.h): on a tile of one plane or triangle
+    // every lane hit that surface, so lane 0 holds the wave's material and
+    // normal (uniform loads), and the tile was shaded (lane 0 is in the frame)
+    if constexpr (LEAN_WR)
+        if (lane == 0 && tiled) {
+            LeanFields f{};
+            f.word = tmask | cls << kTinyClassShift, f.facts = fx | lf << kFactLightShift;
+            f.lean = lean_tile(f.word, f.facts, S.n_lights, S.n_translucent, true);
+            if (tile_facts_kind(fx) == kFactPlane) {  // (a triangle tile's slot is no plane's)
+                const unsigned slot = tile_facts_slot(fx);
+                const float4 a = slot ? PL.a[1] : PL.a[0];
+                f.pn[0] = a.x, f.pn[1] = a.y, f.pn[2] = a.z;
+                f.pnum = slot ? PL.num[1] : PL.num[0];
+            }
+            f.nrm[0] = lean_n.x, f.nrm[1] = lean_n.y, f.nrm[2] = lean_n.z;
+            f.color[0] = lean_m.color.r, f.color[1] = lean_m.color.g, f.color[2] = lean_m.color.b;
+            f.ka = lean_m.ka, f.kd = lean_m.kd, f.ks = lean_m.ks, f.shin = lean_m.shin;
+            H.lean[tile] = lean_pack(f);
+        }
     tile_prof_flush(cnt);
     if (COUNT && (H.flags & RT_FLAG_STATS)) tile_tally(cnt, H.stats, true);  // (every lane runs)
 }
@@ -975,6 +1087,7 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
     struct MaskBuf {
         hipStream_t stream = nullptr;
         TileRec* d = nullptr;  // one record per tile: the word and the tile facts (rt_cull.h)
+        LeanRec* lean = nullptr;  // behind them in the same allocation: one lean record per tile (rt_tile.h)
         size_t cap = 0;
         float key[30] = {};   // the camera whose masks d holds (valid)
         bool valid = false;
@@ -2166,6 +2279,11 @@ static int launch_trace(rt_ctx* c, const KernelPick& kp, const TinyCam* T, Scene
         tiny_head_fill(Lr.h, F, S, *T, c->h_plane.data(),
                        c->d_lrec + (c->opt_lb_region ? 0 : kLightRec * S.n_lights), oa, ob, stats);
         std::memcpy(Lr.rec, T->rec, sizeof Lr.rec);
+#if (RT_TILE_LEAN & 4) != 0
+        // (both sets of light records have the same hot halves)
+        lean_lights_fill(Lr.lights, reinterpret_cast<const float*>(c->h_lrec.data()),
+                         c->h_lrec.size() == (size_t)kLightRec * S.n_lights ? S.n_lights : 0);
+#endif
         args[0] = &Lr;
     }
     HIP_TRY(c, hipLaunchKernel(kp.k, grid, block, args, kp.lds, st));
@@ -3764,7 +3882,8 @@ RT_EXPORT int rt_debug_cb_verify(rt_ctx* c, unsigned long long* out)
 // Diagnostic (include/rt_debug.h): the tile words (rt_cull.h: mask and light
 // classes) a launch-camera render stored for `stream` (tiny_masks; NULL: the
 // synchronous renders' stream), the first n of them.  Synchronous.
-static int tiny_records_read(rt_ctx* c, void* stream, unsigned* out, int n, bool facts)
+// what: 0 the words, 1 the facts, 2 the lean records (16 dwords per tile).
+static int tiny_records_read(rt_ctx* c, void* stream, unsigned* out, int n, int what)
 {
     if (!c || !out || n < 0) return RT_E_ARG;
     if (c->cpu) return not_cpu(c);
@@ -3773,9 +3892,14 @@ static int tiny_records_read(rt_ctx* c, void* stream, unsigned* out, int n, bool
     const hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     for (const auto& q : c->tiny_masks)
         if (q.stream == st && q.valid && q.d && (size_t)n <= q.cap) {
+            if (what == 2) {
+                if (!q.lean) break;
+                HIP_TRY(c, hipMemcpy(out, q.lean, (size_t)n * sizeof(LeanRec), hipMemcpyDeviceToHost));
+                return RT_OK;
+            }
             std::vector<TileRec> h((size_t)n);
             HIP_TRY(c, hipMemcpy(h.data(), q.d, (size_t)n * sizeof(TileRec), hipMemcpyDeviceToHost));
-            for (int i = 0; i < n; ++i) out[i] = facts ? h[(size_t)i].facts : h[(size_t)i].word;
+            for (int i = 0; i < n; ++i) out[i] = what ? h[(size_t)i].facts : h[(size_t)i].word;
             return RT_OK;
         }
     c->err = "no stored tile words of that size for the stream";
@@ -3783,13 +3907,19 @@ static int tiny_records_read(rt_ctx* c, void* stream, unsigned* out, int n, bool
 }
 RT_EXPORT int rt_debug_tiny_words(rt_ctx* c, void* stream, unsigned* out, int n)
 {
-    return tiny_records_read(c, stream, out, n, false);
+    return tiny_records_read(c, stream, out, n, 0);
 }
 // Diagnostic (include/rt_debug.h): the same records' second word, the tile
 // facts (rt_cull.h tile_facts_pack).
 RT_EXPORT int rt_debug_tiny_facts(rt_ctx* c, void* stream, unsigned* out, int n)
 {
-    return tiny_records_read(c, stream, out, n, true);
+    return tiny_records_read(c, stream, out, n, 1);
+}
+// Diagnostic (include/rt_debug.h): the lean records stored beside them
+// (rt_tile.h LeanRec), 16 dwords per tile into out[16 * n_tiles].
+RT_EXPORT int rt_debug_tiny_lean(rt_ctx* c, void* stream, unsigned* out, int n_tiles)
+{
+    return tiny_records_read(c, stream, out, n_tiles, 2);
 }
 
 // Diagnostic (include/rt_debug.h): the last rt_upload_scene's host wall

@@ -1246,5 +1246,53 @@ __device__ __forceinline__ Color shade_local_tiny(const SceneDev& S, const TinyP
     return res;
 }
 
+// shade_local_tiny<1> for a lean tile (rt_tile.h: no translucent surface, at
+// most kTinyClassLights lights, every light classed 1, 2 or 3 in cls): what
+// its loop does when no pass runs the shadow test, without the scene.  Class
+// 3 skips the pass, 1 leaves occ = !gate, 2 sets it; under the gate the
+// filter is then (1, 1, 1) or (0, 0, 0), one value for the wave.  The same
+// operations on the same operands in the same order.
+// BYVAL: the lights' hot halves from the launch record (lv) instead of the
+// light records (lrec).  Each light's is loaded one pass ahead — n0, n1: the
+// first light's, loaded by the caller before the hit —, so that a pass does
+// not begin with a wait.
+template <bool BYVAL>
+__device__ __forceinline__ void lean_light_load(const float4* lrec, const float (*lv)[kLeanLightFloats], int li,
+                                                float4& l0, float4& l1)
+{
+    if constexpr (BYVAL) {
+        const float* v = lv[li];
+        l0 = make_float4(v[0], v[1], v[2], v[3]);
+        l1 = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+        l0 = lrec[kLightRec * li], l1 = lrec[kLightRec * li + 1];
+    }
+}
+template <bool BYVAL>
+__device__ __forceinline__ Color shade_lean_tiny(const float4* lrec, const float (*lv)[kLeanLightFloats], int n_lights,
+                                                 const Mat& m, const Vec3 P, const Vec3 N, const Vec3 D, bool active,
+                                                 unsigned cls, float4 n0, float4 n1)
+{
+    Color res = m.color * m.ka;
+    unsigned rest = cls;
+    for (int li = 0; li < n_lights; ++li) {
+        const float4 l0 = n0, l1 = n1;
+        if (li + 1 < n_lights) lean_light_load<BYVAL>(lrec, lv, li + 1, n0, n1);
+        const unsigned k = rest & 3u;
+        rest >>= 2;
+        if (k == 3u) continue;
+        const Vec3 Lr = make3(l0.x, l0.y, l0.z) - P;
+        const bool gate = active & (dot(Lr, N) > 0);  // Scene.cpp:1756, unnormalised
+        float dist, inv;
+        sqrt_recip_w(Lr.x * Lr.x + Lr.y * Lr.y + Lr.z * Lr.z, dist, inv);
+        const Vec3 L = Lr * inv;
+        if (gate) {
+            const float f = k == 2u ? 0.0f : 1.0f;  // occluded in every gated lane, or in none
+            add_light(res, m, l0, l1, N, L, D, Color{f, f, f});
+        }
+    }
+    return res;
+}
+
 }  // namespace rt
 #endif  // RT_AMD_RT_SHADE_H

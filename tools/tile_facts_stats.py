@@ -1,7 +1,9 @@
 """Counts of the stored tile facts (rt_cull.h tile_facts_pack) of C2, C4 and
 C1 after a camera's second frame, read back through rt_debug_tiny_words and
 rt_debug_tiny_facts: tiles by kind, and per light the no-op and all-gated
-pairs against the light's class.  One JSON line.
+pairs against the light's class; and the lean tiles (rt_tile.h): by the rule,
+from the two words, and as the stored lean records flag them
+(rt_debug_tiny_lean).  One JSON line.
 
     python tools/tile_facts_stats.py > profiles/r13/tile_facts/fact_stats.json
 """
@@ -39,5 +41,18 @@ for cfg in ("c2", "c4", "c1"):
                             "all_gated_class1": int(((b & 2 != 0) & (k == 1)).sum()),
                             "noop_class": [int(((b & 1 != 0) & (k == q)).sum()) for q in range(3)],
                             "class": [int((k == q).sum()) for q in range(3)]})
+    # lean: one plane or kept triangle with a known index, every light classed (a no-op counts), no translucent surface
+    lean = ((kind == 1) | (kind == 2)) & (fx >> 20 != 0)
+    for li in range(nl):
+        lean &= ((wd >> (20 + 2 * li) & 3) != 0) | ((fx >> (8 + 2 * li) & 1) != 0)
+    if (s.arrays()[2][:, 8] != 0).any() or nl > 6:
+        lean[:] = False
+    d["lean_by_rule"] = int(lean.sum())
+    d["lean_plane"], d["lean_triangle"] = int((lean & (kind == 1)).sum()), int((lean & (kind == 2)).sum())
+    f = L.rt_debug_tiny_lean; f.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int]; f.restype = ctypes.c_int
+    rec = np.zeros(ty * tx * 16, np.uint32)
+    assert f(c._h, None, rec.ctypes.data, ty * tx) == 0
+    rk = rec.reshape(-1, 16)[:, 1] & 7
+    d["lean_stored"] = int(((rk == 5) | (rk == 6)).sum())
     out[cfg] = d
 print(json.dumps(out))
