@@ -308,6 +308,49 @@ int rt_render_aov(rt_ctx*, const rt_frame*, const rt_aov* out);  /* sync; host o
 int rt_render_aov_async(rt_ctx*, const rt_frame*, const rt_aov* dev, void* hip_stream); /* device ptrs */
 int rt_cpu_render_aov(rt_ctx*, const rt_frame*, const rt_aov* out);                     /* CPU backend */
 
+/* Closest-hit queries of arbitrary rays — an addition within ABI 8
+ * (rt_abi_version() stays 8; test for RT_HAS_RAYS): "what does THIS ray hit",
+ * as CScene::ObtenirCouleur's search (Scene.cpp:1705-1715) decides it, for
+ * picking, line of sight, collision probes and a caller's own secondary rays.
+ * Input.  rays: n records of 6 floats [Ox Oy Oz Dx Dy Dz] (a C-order (n, 6)
+ * float32 array).  The direction is used AS GIVEN: CRayon::AjusterDirection
+ * does not normalise, so t is in units of |D|.
+ * Output.  `out` reuses rt_aov as planes of n entries: t (float32), id (int32,
+ * the file index), n (3 x float32 per ray); each may be NULL, not all three.
+ * Definition.  Over the surfaces in file order, surface i with distance t_i
+ * replaces the current winner when
+ *   t_i > EPSILON && (t_i < t_best || t_best < 0)
+ * (a tie keeps the earlier surface); a miss is -1 / -1.0f / (0, 0, 0); the
+ * normal is the winner's ObtenirNormale(): triangles and planes the stored
+ * post-Pretraitement normal, quadrics the normalised gradient at the hit —
+ * exactly rt_render_aov's values, so the AOV planes of a frame equal a ray
+ * query of that frame's camera rays, bit for bit.
+ * rt_trace_rays is synchronous; each of its four pointers is independently a
+ * host or a device pointer (as in rt_render_aov).  rt_last_stats afterwards:
+ * kernel ("rt_rays_kernel<0>": every surface per ray; "rt_rays_kernel<1>":
+ * the triangles through the exact BVH, csrc/rt_rays.h), kernel_ms,
+ * bounce_rays = n, primary_rays = 0.
+ * rt_trace_rays_async takes device pointers only and enqueues one kernel on
+ * `hip_stream`: it allocates nothing, builds nothing and reads or writes no
+ * device state of the context besides the uploaded scene, so it needs no
+ * ordering against any render and can be recorded into a hipGraph capture
+ * unconditionally (a context that has never rendered included).  As for
+ * rt_render_async, rt_upload_scene syncs the streams used here first, and a
+ * stream must stay alive until the next synchronous call returns.
+ * A query walks the BVH whenever the uploaded scene has one (at least 64
+ * triangles and a reflective or refractive surface, or RT_OPT_RAY_BVH) and
+ * RT_OPT_BVH is 1; else it tests every surface: the same bits either way.
+ * Device pointers must be 8-byte aligned.
+ * RT_OK and nothing written: n == 0.  RT_E_ARG: n < 0 or n > INT32_MAX, a NULL
+ * rays / out, all three planes NULL, a misaligned device pointer, a host
+ * pointer given to rt_trace_rays_async.  RT_E_STATE: before rt_upload_scene,
+ * or on the other backend's context (rt_cpu_trace_rays is the CPU backend's:
+ * host pointers, the same bits). */
+#define RT_HAS_RAYS 1
+int rt_trace_rays(rt_ctx*, const float* rays, int64_t n, const rt_aov* out);            /* sync; host or device ptrs */
+int rt_trace_rays_async(rt_ctx*, const float* dev_rays, int64_t n, const rt_aov* dev_out, void* hip_stream);
+int rt_cpu_trace_rays(rt_ctx*, const float* rays, int64_t n, const rt_aov* out);        /* CPU backend */
+
 /* ABI 4: context options.  A/B and test switches and tuning knobs; no option
  * changes a single bit of any image.  Upload options take effect at the next
  * rt_upload_scene, launch options at the next render.                      */
@@ -404,6 +447,13 @@ enum {
  * A skipped lookup would have read an empty list: never changes an image or
  * a tally. */
 #define RT_OPT_LB_REGION 21
+/* Added within ABI 8 with the ray queries (a macro like the ones above).
+ * Upload: 1 builds the bounce-ray BVH also for a scene with no reflective or
+ * refractive surface (still at least 64 triangles, and a tree that fits the
+ * walk's stack), for rt_trace_rays* alone: such a scene has no bounce rays,
+ * and no colour frame, AOV frame or wavefront decision reads that tree.
+ * Default 0: the build costs upload time and memory on big meshes. */
+#define RT_OPT_RAY_BVH 22
 int rt_set_option(rt_ctx*, int32_t option, double value);
 int rt_get_option(rt_ctx*, int32_t option, double* value);
 /* ABI 4, upload: the far light-buffer ladder of big lists — rising distance

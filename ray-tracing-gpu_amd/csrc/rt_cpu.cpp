@@ -450,6 +450,45 @@ int cpu_render_aov(const void* handle, int threads, const rt_frame* f, int rows,
     return RT_OK;
 }
 
+// Ray queries (rt.h rt_trace_rays): closest and normal_of per ray, chunks of
+// kChunk rays handed to the host threads from an atomic counter.
+int cpu_trace_rays(const void* handle, int threads, const float* rays, int64_t n, float* out_t, int32_t* out_id,
+                   float* out_n, double* ms)
+{
+    using namespace cpu;
+    const Scene& S = *static_cast<const Scene*>(handle);
+    const auto t0 = std::chrono::steady_clock::now();
+    std::atomic<int64_t> next{0};
+    constexpr int64_t kChunk = 256;
+    auto work = [&]() {
+        for (;;) {
+            const int64_t i0 = next.fetch_add(kChunk);
+            if (i0 >= n) return;
+            for (int64_t i = i0; i < std::min(n, i0 + kChunk); ++i) {
+                const float* r = rays + 6 * (size_t)i;
+                const Vec3 O = make3(r[0], r[1], r[2]), D = make3(r[3], r[4], r[5]);
+                const Hit h = closest(S, O, D);
+                if (out_t) out_t[i] = h.file < 0 ? -1.0f : h.t;
+                if (out_id) out_id[i] = h.file;
+                if (out_n) {
+                    const Vec3 N = h.file < 0 ? make3(0.0f, 0.0f, 0.0f) : normal_of(S, h.file, O, D, h.t);
+                    out_n[3 * i] = N.x;
+                    out_n[3 * i + 1] = N.y;
+                    out_n[3 * i + 2] = N.z;
+                }
+            }
+        }
+    };
+    int64_t k = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());
+    k = std::max<int64_t>(1, std::min(k, (n + kChunk - 1) / kChunk));
+    std::vector<std::thread> pool;
+    for (int64_t i = 1; i < k; ++i) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
 void cpu_resolve(const float* samples, int width, int s, int rows_out, uint8_t* rgba, float* rgb, double* ms)
 {
     const auto t0 = std::chrono::steady_clock::now();

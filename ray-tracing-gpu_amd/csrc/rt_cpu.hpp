@@ -18,6 +18,11 @@ int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uin
 // index, normal; a miss is -1, -1, 0); each output may be null.
 int cpu_render_aov(const void* handle, int threads, const rt_frame* f, int rows, float* t, int32_t* id, float* n,
                    double* ms);
+// Closest-hit queries of n arbitrary rays (rt.h rt_trace_rays: 6 floats per
+// ray, O then D, the direction as given; planes of n entries, each may be
+// null; a miss is -1, -1, 0): rt_rays_kernel's values bit for bit.
+int cpu_trace_rays(const void* handle, int threads, const float* rays, int64_t n, float* t, int32_t* id, float* nrm,
+                   double* ms);
 // The supersampling resolve (rt_resolve.h resolve_px, the HIP kernel's own
 // arithmetic): rows_out rows of width / s pixels from their packed sample
 // rows; either output may be null.  *ms = wall time.

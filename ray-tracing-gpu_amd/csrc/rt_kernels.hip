@@ -45,6 +45,7 @@
 #include "rt_scan.h"
 #include "rt_shade.h"
 #include "rt_bvh.h"
+#include "rt_rays.h"
 #include "rt_wavefront.h"
 #include "rt_resolve.h"
 #include "rt_scenehost.h"  // scene_host_build, lb_plan; RT_BVH_MIN_TRIANGLES
@@ -1140,6 +1141,7 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
     int bvh_inner = 0, bvh_leaves = 0, bvh_depth = 0;
     double bvh_build_ms = 0.0;
     bool opt_bvh = true;        // RT_OPT_BVH
+    bool opt_ray_bvh = false;   // RT_OPT_RAY_BVH: the BVH also for scenes without bounce rays (ray queries)
     // Wavefront bounce queues (rt_wavefront.h), grown on demand; one set per
     // context: a wavefront frame on another stream than the last one's waits
     // for that frame (turn) before it reuses them.
@@ -1397,6 +1399,7 @@ RT_EXPORT int rt_set_option(rt_ctx* c, int32_t opt, double v)
         return RT_OK;
     case RT_OPT_LAUNCH_CAMERA: c->opt_launch_camera = v != 0; return RT_OK;
     case RT_OPT_BVH: c->opt_bvh = v != 0; return RT_OK;
+    case RT_OPT_RAY_BVH: c->opt_ray_bvh = v != 0; return RT_OK;
     case RT_OPT_WAVEFRONT: c->opt_wavefront = v != 0; return RT_OK;
     case RT_OPT_WF_SORT:
         if (v < 0 || v > 7 || v != std::floor(v)) return RT_E_ARG;
@@ -1440,6 +1443,7 @@ RT_EXPORT int rt_get_option(rt_ctx* c, int32_t opt, double* v)
     case RT_OPT_CB_CAPACITY: *v = c->opt_cb_capacity; return RT_OK;
     case RT_OPT_LAUNCH_CAMERA: *v = c->opt_launch_camera ? 1 : 0; return RT_OK;
     case RT_OPT_BVH: *v = c->opt_bvh ? 1 : 0; return RT_OK;
+    case RT_OPT_RAY_BVH: *v = c->opt_ray_bvh ? 1 : 0; return RT_OK;
     case RT_OPT_WAVEFRONT: *v = c->opt_wavefront; return RT_OK;
     case RT_OPT_WF_SORT: *v = c->opt_wf_sort; return RT_OK;
     case RT_OPT_WF_OVERLAP: *v = c->opt_wf_overlap ? 1 : 0; return RT_OK;
@@ -2141,7 +2145,7 @@ RT_EXPORT int rt_upload_scene(rt_ctx* c, const rt_scene_flat* s)
     free_retired(c);
     const auto tu0 = std::chrono::steady_clock::now();
     SceneHost H;
-    if (!scene_host_build(s, H, c->err)) return RT_E_ARG;  // (the context is as it was)
+    if (!scene_host_build(s, H, c->err, c->opt_ray_bvh)) return RT_E_ARG;  // (the context is as it was)
     scene_drop(c);
     if (int rc = upload_records(c, H)) return rc;
     if (int rc = upload_bvh(c, H)) return rc;
@@ -2412,10 +2416,14 @@ static bool lbuf_on(const rt_ctx* c)
     return c->lb_ready && (mode == 1 || (mode == 2 && c->n_tri > kClusterMinTriangles));
 }
 // Bounce rays walk the BVH (rt_bvh.h) in the frame's kernel (the BVH kernels
-// take their shadow rays through the light buffer).
+// take their shadow rays through the light buffer).  k_max > 0: the scene can
+// bounce — a BVH built for ray queries alone (RT_OPT_RAY_BVH) belongs to a
+// scene whose frames never had one, whatever depth they ask for (a negative
+// min_energy makes every depth reachable), and must not move them to the BVH
+// kernels.
 static bool bvh_on(const rt_ctx* c, int depth, bool lbuf)
 {
-    return depth > 0 && c->d_bvh_node && c->opt_bvh && lbuf && c->n_tri > 0;
+    return depth > 0 && c->d_bvh_node && c->k_max > 0.0f && c->opt_bvh && lbuf && c->n_tri > 0;
 }
 // No refracted ray can pass its gate (Scene.cpp:1791: Kt * energy >
 // min_energy with every Kt <= 0 and min_energy >= 0): the bounce tree of
@@ -3638,6 +3646,134 @@ RT_EXPORT int rt_cpu_render_aov(rt_ctx* c, const rt_frame* f, const rt_aov* out)
     c->last.kernel_ms = (float)ms;
     c->last.primary_rays = (uint64_t)f->width * (uint64_t)ss_valid_rows(f, rows);
     std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_render_aov");
+    return rc;
+}
+
+// ---- closest-hit queries of arbitrary rays (rt.h rt_trace_rays*, rt_rays.h)
+// The checks every ray entry point shares (after the backend's own).  *go:
+// there is something to trace (n == 0 is RT_OK with nothing written).
+static int rays_check(rt_ctx* c, const float* rays, int64_t n, const rt_aov* o, bool* go)
+{
+    *go = false;
+    if (int rc = check_uploaded(c, "rt_trace_rays")) return rc;
+    if (n < 0 || n > INT32_MAX) {
+        c->err = "rt_trace_rays: the ray count must be 0 .. INT32_MAX";
+        return RT_E_ARG;
+    }
+    if (n == 0) return RT_OK;
+    if (!rays || !o || (!o->t && !o->id && !o->n)) {
+        c->err = "rt_trace_rays: no rays or no output plane";
+        return RT_E_ARG;
+    }
+    *go = true;
+    return RT_OK;
+}
+
+static int rays_aligned(rt_ctx* c, const void* p)
+{
+    if (((uintptr_t)p & 7u) == 0) return RT_OK;
+    c->err = "rt_trace_rays: device pointers must be 8-byte aligned";
+    return RT_E_ARG;
+}
+
+// The query walks the BVH whenever the scene has one (RT_OPT_BVH): the tree
+// of a scene that can bounce, or RT_OPT_RAY_BVH's.
+static bool rays_bvh(const rt_ctx* c) { return c->d_bvh_node && c->opt_bvh; }
+
+// n rays into device planes on st: one kernel, no state of the context.
+static int launch_rays(rt_ctx* c, const float* d_rays, int n, const rt_aov& dev, hipStream_t st)
+{
+    const bool bvh = rays_bvh(c);
+    SceneDev S = scene_dev(c, c->cam, false, false);
+    const float2* rays = reinterpret_cast<const float2*>(d_rays);
+    float* ot = dev.t;
+    int* oi = dev.id;
+    float* on = dev.n;
+    void* args[] = {&S, &rays, &n, &ot, &oi, &on};
+    const void* k = bvh ? (const void*)&rt_rays_kernel<1> : (const void*)&rt_rays_kernel<0>;
+    const unsigned lds = bvh ? (unsigned)rays_lds_bytes(c->bvh_depth) : 0u;
+    HIP_TRY(c, hipLaunchKernel(k, dim3((unsigned)(((int64_t)n + 63) / 64)), dim3(64), args, lds, st));
+    return RT_OK;
+}
+
+RT_EXPORT int rt_trace_rays(rt_ctx* c, const float* rays, int64_t n, const rt_aov* out)
+{
+    if (!c) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    bool go;
+    if (int rc = rays_check(c, rays, n, out, &go)) return rc;
+    if (!go) return RT_OK;
+    if (int rc = sync_begin(c)) return rc;
+    // the scratch: a host ray array first, then one 256-byte aligned part per host plane
+    const bool rays_host = !is_device_ptr(rays);
+    const size_t rbytes = (size_t)n * 6 * sizeof(float);
+    void* const user[3] = {out->t, out->id, out->n};
+    SyncOut o;
+    if (rays_host) o.need = (rbytes + 255) / 256 * 256;
+    for (int i = 0; i < 3; ++i) o.add(user[i], ((size_t)n * (i == 2 ? 12 : 4) + 255) / 256 * 256);
+    if (!rays_host)
+        if (int rc = rays_aligned(c, rays)) return rc;
+    for (int i = 0; i < 3; ++i)
+        if (user[i] && !o.host[i])
+            if (int rc = rays_aligned(c, user[i])) return rc;
+    if (int rc = o.place(c)) return rc;
+    const float* d_rays = rays;
+    if (rays_host) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_scratch, rays, rbytes, hipMemcpyHostToDevice, c->stream));
+        d_rays = (const float*)c->d_scratch;
+    }
+    const rt_aov dev{(float*)o.target[0], (int32_t*)o.target[1], (float*)o.target[2]};
+    c->last = rt_stats{};
+    std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_rays_kernel<%d>", rays_bvh(c) ? 1 : 0);
+    c->last.bounce_rays = (uint64_t)n;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    if (int rc = launch_rays(c, d_rays, (int)n, dev, c->stream)) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    for (int i = 0; i < 3; ++i)
+        if (int rc = o.copy_back(c, i, (size_t)n * (i == 2 ? 12 : 4))) return rc;
+    static const rt_frame no_frame{};  // (no RT_FLAG_STATS)
+    return finish_sync(c, &no_frame, c->stream, true);
+}
+
+RT_EXPORT int rt_trace_rays_async(rt_ctx* c, const float* dev_rays, int64_t n, const rt_aov* dev, void* stream)
+{
+    if (!c) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    bool go;
+    if (int rc = rays_check(c, dev_rays, n, dev, &go)) return rc;
+    if (!go) return RT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const void* const ptr[4] = {dev_rays, dev->t, dev->id, dev->n};
+    for (const void* p : ptr) {
+        if (!p) continue;
+        if (!is_device_ptr(p)) {
+            c->err = "rt_trace_rays_async takes device pointers";
+            return RT_E_ARG;
+        }
+        if (int rc = rays_aligned(c, p)) return rc;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    bool capturing = false;
+    if (int rc = stream_capturing(c, st, &capturing)) return rc;
+    if (int rc = launch_rays(c, dev_rays, (int)n, *dev, st)) return rc;
+    // (host bookkeeping only: an upload syncs st, or keeps what a graph references)
+    enqueued(c, st, capturing, nullptr);
+    return RT_OK;
+}
+
+RT_EXPORT int rt_cpu_trace_rays(rt_ctx* c, const float* rays, int64_t n, const rt_aov* out)
+{
+    if (!c) return RT_E_ARG;
+    if (!c->cpu) return needs_cpu(c, "rt_cpu_trace_rays");
+    bool go;
+    if (int rc = rays_check(c, rays, n, out, &go)) return rc;
+    if (!go) return RT_OK;
+    c->last = rt_stats{};
+    double ms = 0.0;
+    const int rc = cpu_trace_rays(c->cpu_scene, c->cpu_threads, rays, n, out->t, out->id, out->n, &ms);
+    c->last.kernel_ms = (float)ms;
+    c->last.bounce_rays = (uint64_t)n;
+    std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_trace_rays");
     return rc;
 }
 

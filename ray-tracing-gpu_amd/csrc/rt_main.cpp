@@ -3,7 +3,7 @@
 //   rt_render <scene.dat> [-x W] [-y H] [-d depth] [-o out.ppm] [-g gpus]
 //             [--device first] [--bands] [-n frames] [-s]
 //             [--gather rccl|host] [--backend hip|cpu] [--threads N]
-//             [--ssaa N] [--aov PREFIX]
+//             [--ssaa N] [--aov PREFIX] [--rays IN.npy --hits PREFIX [--ray-bvh]]
 //
 // Kept from Main.cpp:51-199: argv[1] is the scene file, -x / -y set the
 // resolution (default 512x256, Var.cpp:4-5), the same [ETAT]/[ERREUR] log
@@ -39,6 +39,13 @@
 // H x W) and PREFIX_n.npy (float32, H x W x 3): NumPy format 1.0,
 // little-endian, row 0 = the bottom scanline like the library (with --ssaa:
 // of the N W x N H sample grid); on either backend, one GPU.
+// --rays IN.npy --hits PREFIX traces the caller's own rays (rt_trace_rays /
+// rt_cpu_trace_rays): IN.npy is a little-endian float32 (N, 6) C-order array
+// [Ox Oy Oz Dx Dy Dz] in NumPy format 1.0 or 2.0, and PREFIX_t.npy (float32,
+// N), PREFIX_id.npy (int32, N) and PREFIX_n.npy (float32, N x 3) are written
+// by --aov's writer; on either backend, one GPU; --ray-bvh sets
+// RT_OPT_RAY_BVH for the upload.  The frame itself is then rendered only when
+// -o names a file.
 #include <hip/hip_runtime_api.h>
 
 #include <dlfcn.h>
@@ -82,7 +89,9 @@ static int write_npy(const std::string& path, const char* descr, int rows, int w
                      size_t bytes)
 {
     char shape[64];
-    if (comps > 1)
+    if (width <= 0)  // one-dimensional (--hits: a value per ray)
+        std::snprintf(shape, sizeof shape, "(%d,)", rows);
+    else if (comps > 1)
         std::snprintf(shape, sizeof shape, "(%d, %d, %d)", rows, width, comps);
     else
         std::snprintf(shape, sizeof shape, "(%d, %d)", rows, width);
@@ -118,6 +127,112 @@ static int write_aov(rt_ctx* c, bool cpu, rt_frame frame, const char* prefix)
     if (write_npy(p + "_t.npy", "<f4", H, W, 1, t.data(), px * 4)) return fail("fopen", -1, (p + "_t.npy").c_str());
     if (write_npy(p + "_id.npy", "<i4", H, W, 1, id.data(), px * 4)) return fail("fopen", -1, (p + "_id.npy").c_str());
     if (write_npy(p + "_n.npy", "<f4", H, W, 3, n.data(), px * 12)) return fail("fopen", -1, (p + "_n.npy").c_str());
+    return 0;
+}
+
+// --rays: a NumPy format 1.0 / 2.0 file holding a little-endian float32
+// (N, 6) C-order array.  false with `why` set for anything else.
+static bool read_rays_npy(const char* path, std::vector<float>& rays, std::string& why)
+{
+    FILE* f = std::fopen(path, "rb");
+    if (!f) {
+        why = "cannot open the file";
+        return false;
+    }
+    std::vector<unsigned char> raw;
+    unsigned char buf[65536];
+    size_t got;
+    while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) raw.insert(raw.end(), buf, buf + got);
+    std::fclose(f);
+    static const unsigned char magic[6] = {0x93, 'N', 'U', 'M', 'P', 'Y'};
+    if (raw.size() < 10 || std::memcmp(raw.data(), magic, 6) != 0) {
+        why = "not a .npy file";
+        return false;
+    }
+    size_t hlen, hoff;
+    if (raw[6] == 1 && raw[7] == 0) {
+        hlen = (size_t)raw[8] | ((size_t)raw[9] << 8);
+        hoff = 10;
+    } else if (raw[6] == 2 && raw[7] == 0 && raw.size() >= 12) {
+        hlen = (size_t)raw[8] | ((size_t)raw[9] << 8) | ((size_t)raw[10] << 16) | ((size_t)raw[11] << 24);
+        hoff = 12;
+    } else {
+        why = ".npy format version 1.0 or 2.0 only";
+        return false;
+    }
+    if (hlen > raw.size() - hoff) {
+        why = "truncated header";
+        return false;
+    }
+    const std::string h((const char*)raw.data() + hoff, hlen);
+    // the value that follows 'key': up to the next top-level comma
+    auto value = [&](const char* key, std::string& v) {
+        const size_t k = h.find(std::string("'") + key + "'");
+        if (k == std::string::npos) return false;
+        size_t a = h.find(':', k);
+        if (a == std::string::npos) return false;
+        ++a;
+        while (a < h.size() && h[a] == ' ') ++a;
+        size_t b = a;
+        int par = 0;
+        while (b < h.size() && !((h[b] == ',' || h[b] == '}') && par == 0)) {
+            par += h[b] == '(' ? 1 : h[b] == ')' ? -1 : 0;
+            ++b;
+        }
+        while (b > a && h[b - 1] == ' ') --b;
+        v = h.substr(a, b - a);
+        return true;
+    };
+    std::string descr, order, shape;
+    if (!value("descr", descr) || !value("fortran_order", order) || !value("shape", shape)) {
+        why = "header without descr / fortran_order / shape";
+        return false;
+    }
+    if (descr != "'<f4'" && descr != "\"<f4\"") {
+        why = "dtype " + descr + ": little-endian float32 ('<f4') only";
+        return false;
+    }
+    if (order != "False") {
+        why = "Fortran order: C order only";
+        return false;
+    }
+    long long n = -1;
+    int cols = -1, used = 0;
+    if (std::sscanf(shape.c_str(), "(%lld , %d )%n", &n, &cols, &used) != 2 || used != (int)shape.size() || cols != 6 ||
+        n < 0 || n > INT32_MAX) {
+        why = "shape " + shape + ": (N, 6) only";
+        return false;
+    }
+    const size_t bytes = (size_t)n * 6 * sizeof(float);
+    if (raw.size() - hoff - hlen != bytes) {
+        why = "the data are not N x 6 x 4 bytes";
+        return false;
+    }
+    rays.resize((size_t)n * 6);
+    if (bytes) std::memcpy(rays.data(), raw.data() + hoff + hlen, bytes);
+    return true;
+}
+
+// --rays / --hits: the closest hits of the file's rays from context c (either backend).
+static int write_hits(rt_ctx* c, bool cpu, const std::vector<float>& rays, const char* prefix)
+{
+    const uint16_t probe = 1;
+    if (*(const unsigned char*)&probe != 1) return fail("--hits", RT_E_UNSUPPORTED, "little-endian hosts only");
+    const size_t n = rays.size() / 6;
+    std::vector<float> t(n), nrm(n * 3);
+    std::vector<int32_t> id(n);
+    const rt_aov out{t.data(), id.data(), nrm.data()};
+    const int rc = n == 0 ? 0
+                   : cpu  ? rt_cpu_trace_rays(c, rays.data(), (int64_t)n, &out)
+                          : rt_trace_rays(c, rays.data(), (int64_t)n, &out);
+    if (rc) return fail("rt_trace_rays", rc, rt_last_error(c));
+    rt_stats st;
+    rt_last_stats(c, &st);
+    if (n) std::printf("[ETAT]: %zu rayons, %s, %.3f ms\n", n, st.kernel, st.kernel_ms);
+    const std::string p(prefix);
+    if (write_npy(p + "_t.npy", "<f4", (int)n, 0, 1, t.data(), n * 4)) return fail("fopen", -1, (p + "_t.npy").c_str());
+    if (write_npy(p + "_id.npy", "<i4", (int)n, 0, 1, id.data(), n * 4)) return fail("fopen", -1, (p + "_id.npy").c_str());
+    if (write_npy(p + "_n.npy", "<f4", (int)n, 3, 1, nrm.data(), n * 12)) return fail("fopen", -1, (p + "_n.npy").c_str());
     return 0;
 }
 
@@ -355,6 +470,9 @@ int main(int argc, char** argv)
     int gather = -1;  // -1 auto (RCCL for -g > 1 on distinct GPUs), 0 host, 1 RCCL
     const char* out = nullptr;
     const char* aov = nullptr;
+    const char* rays_in = nullptr;
+    const char* hits = nullptr;
+    bool ray_bvh = false;
     for (int i = 2; i < argc; ++i) {
         if (argv[i][0] != '-') continue;
         auto next = [&](int& v) {
@@ -377,6 +495,20 @@ int main(int argc, char** argv)
         if (std::strcmp(argv[i], "--aov") == 0) {
             if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--aov needs a file prefix");
             aov = argv[++i];
+            continue;
+        }
+        if (std::strcmp(argv[i], "--rays") == 0) {
+            if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--rays needs a .npy file");
+            rays_in = argv[++i];
+            continue;
+        }
+        if (std::strcmp(argv[i], "--hits") == 0) {
+            if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--hits needs a file prefix");
+            hits = argv[++i];
+            continue;
+        }
+        if (std::strcmp(argv[i], "--ray-bvh") == 0) {
+            ray_bvh = true;
             continue;
         }
         if (std::strcmp(argv[i], "--threads") == 0) {
@@ -427,6 +559,17 @@ int main(int argc, char** argv)
     if (aov && (gpus != 1 || bands || gather == 1))
         return fail("arguments", RT_E_ARG,
                     "--aov renders on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
+    if ((rays_in != nullptr) != (hits != nullptr))
+        return fail("arguments", RT_E_ARG, "--rays IN.npy and --hits PREFIX go together");
+    if (rays_in && (gpus != 1 || bands || gather == 1))
+        return fail("arguments", RT_E_ARG,
+                    "--rays traces on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
+    if (ray_bvh && !rays_in) return fail("arguments", RT_E_ARG, "--ray-bvh goes with --rays");
+    std::vector<float> rays;
+    if (rays_in) {
+        std::string why;
+        if (!read_rays_npy(rays_in, rays, why)) return fail("--rays", RT_E_ARG, (std::string(rays_in) + ": " + why).c_str());
+    }
     if (((W - 1) & W) || ((H - 1) & H))
         std::fprintf(stderr, "[ATTENTION]: Resolution %dx%d n'est pas une puissance de deux "
                              "(accepted: the render core has no such restriction)\n", W, H);
@@ -445,6 +588,31 @@ int main(int argc, char** argv)
     rt_scene_get_frame(scene, &frame);
     if (stats) frame.flags |= RT_FLAG_STATS;
 
+    if (rays_in) {  // ray queries: one context of either backend; the frame only for -o
+        rt_ctx* c = nullptr;
+        if (cpu) {
+            if ((rc = rt_create_cpu(threads, &c))) return fail("rt_create_cpu", rc, "");
+        } else {
+            int nd = 0;
+            if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return fail("rt_create", RT_E_HIP, "no HIP device");
+            if ((rc = rt_create(dev0 % nd, &c))) return fail("rt_create", rc, c ? rt_last_error(c) : "");
+        }
+        if (ray_bvh && (rc = rt_set_option(c, RT_OPT_RAY_BVH, 1.0))) return fail("rt_set_option", rc, rt_last_error(c));
+        if ((rc = rt_upload_scene(c, &flat))) return fail("rt_upload_scene", rc, rt_last_error(c));
+        std::printf("[ETAT]: Lancer de rayons (%zu rayons de %s)...\n", rays.size() / 6, rays_in);
+        if (write_hits(c, cpu, rays, hits)) return 1;
+        if (out) {
+            std::vector<uint8_t> img((size_t)W * H * 4);
+            rc = cpu ? (ssaa > 1 ? rt_cpu_render_ss(c, &frame, ssaa, img.data()) : rt_cpu_render(c, &frame, img.data()))
+                     : (ssaa > 1 ? rt_render_ss(c, &frame, ssaa, img.data()) : rt_render(c, &frame, img.data()));
+            if (rc) return fail("LancerRayons", rc, rt_last_error(c));
+            if (write_ppm(out, W, H, img)) return fail("fopen", -1, out);
+        }
+        if (aov && write_aov(c, cpu, frame, aov)) return 1;
+        rt_destroy(c);
+        rt_scene_destroy(scene);
+        return 0;
+    }
     if (cpu) {  // the CPU backend: one context, host threads
         if (gpus != 1 || bands) return fail("arguments", RT_E_ARG, "-g / --bands are for the hip backend");
         rt_ctx* c = nullptr;

@@ -288,9 +288,12 @@ inline void scene_host_tri_records(SceneHost& H)
 // The bounce-ray BVH: only a scene with a reflective or refractive surface
 // has bounce rays (Scene.cpp:1779-1823 gate on Kr, Kt > 0).  A tree deeper
 // than the walk's stack is dropped (bounce rays then test every triangle).
-inline void scene_host_bvh(SceneHost& H)
+// ray_bvh (RT_OPT_RAY_BVH): also a scene that cannot bounce gets the tree, for
+// rt_trace_rays — the same size limits; its frames never use it (bvh_on).
+inline void scene_host_bvh(SceneHost& H, bool ray_bvh = false)
 {
-    if (!(H.k_max > 0.0f && H.n_tri >= RT_BVH_MIN_TRIANGLES && (size_t)H.n_tri <= kBvhMaxTriangles)) return;
+    if (!((H.k_max > 0.0f || ray_bvh) && H.n_tri >= RT_BVH_MIN_TRIANGLES && (size_t)H.n_tri <= kBvhMaxTriangles))
+        return;
     const auto tb = std::chrono::steady_clock::now();
     bvh_build(H.tri, (size_t)H.n_tri, H.bvh);
     if (H.bvh.depth <= kBvhStack) {
@@ -321,11 +324,11 @@ inline void scene_host_bvh(SceneHost& H)
 
 // The host half of an upload.  false with err set ("unknown surface type"):
 // H is untouched.
-inline bool scene_host_build(const rt_scene_flat* s, SceneHost& H, std::string& err)
+inline bool scene_host_build(const rt_scene_flat* s, SceneHost& H, std::string& err, bool ray_bvh = false)
 {
     if (!scene_host_records(s, H, err)) return false;
     scene_host_lists(s, H);
-    scene_host_bvh(H);
+    scene_host_bvh(H, ray_bvh);
     scene_host_tri_records(H);
     return true;
 }

@@ -24,7 +24,7 @@ import numpy as np
 
 __all__ = [
     "RtError", "SceneFlat", "Frame", "Stats", "Aov", "Scene", "Context", "CpuContext", "CScene", "lib", "band_rows",
-    "frame_rows", "ss_rows", "SS_OPTIONS", "LB_OPTIONS",
+    "frame_rows", "ss_rows", "SS_OPTIONS", "LB_OPTIONS", "RAY_OPTIONS",
     "LIB_PATH", "TRIANGLE", "PLANE", "QUADRIC", "FLAG_STATS", "OPTIONS", "camera_path",
 ]
 
@@ -41,6 +41,8 @@ OPTIONS = {"light_buffer": 1, "camera_buffer": 2, "union_pretest": 3, "lb_scale"
 SS_OPTIONS = {"ss_chunk_rows": 20}
 # (RT_OPT_LB_REGION: the launch-camera kernels' occupied-direction test, 1 / 0)
 LB_OPTIONS = {"lb_region": 21}
+# (RT_OPT_RAY_BVH, upload: the BVH also for a scene that cannot bounce, for trace_rays; 1 / 0, default 0)
+RAY_OPTIONS = {"ray_bvh": 22}
 _ERRORS = {-1: "RT_E_ARG", -2: "RT_E_IO", -3: "RT_E_PARSE", -4: "RT_E_STATE", -5: "RT_E_HIP",
            -6: "RT_E_UNSUPPORTED"}
 
@@ -125,6 +127,9 @@ SIGNATURES = {
     "rt_render_aov": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Aov)]),
     "rt_render_aov_async": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Aov), _VP]),
     "rt_cpu_render_aov": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Aov)]),
+    "rt_trace_rays": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(Aov)]),
+    "rt_trace_rays_async": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(Aov), _VP]),
+    "rt_cpu_trace_rays": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(Aov)]),
     "rt_upload_scene": (ctypes.c_int, [_VP, ctypes.POINTER(SceneFlat)]),
     "rt_render": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
     "rt_render_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
@@ -181,9 +186,27 @@ def _aov_planes(frame: "Frame", t: bool, id: bool, n: bool):
     return out, aov
 
 
+def _ray_planes(rays, t: bool, id: bool, n: bool):
+    """The (N, 6) float32 ray array, host arrays for the requested planes of N
+    entries and the rt_aov that points at them."""
+    r = np.ascontiguousarray(rays, np.float32)
+    if r.ndim != 2 or r.shape[1] != 6:
+        raise ValueError("rays: an (N, 6) array [Ox Oy Oz Dx Dy Dz]")
+    count = r.shape[0]
+    out = {}
+    if t:
+        out["t"] = np.zeros(count, np.float32)
+    if id:
+        out["id"] = np.zeros(count, np.int32)
+    if n:
+        out["n"] = np.zeros((count, 3), np.float32)
+    aov = Aov(*(out[k].ctypes.data if k in out else None for k in ("t", "id", "n")))
+    return r, out, aov
+
+
 def _option(name) -> int:
     if isinstance(name, str):
-        for table in (OPTIONS, SS_OPTIONS, LB_OPTIONS):
+        for table in (OPTIONS, SS_OPTIONS, LB_OPTIONS, RAY_OPTIONS):
             if name in table:
                 return table[name]
         raise KeyError(name)
@@ -283,7 +306,7 @@ class Context:
                 self.set_option(k, v)
 
     def set_option(self, name, value: float):
-        """rt_set_option: `name` is a key of OPTIONS, SS_OPTIONS or LB_OPTIONS (or the RT_OPT_* number)."""
+        """rt_set_option: `name` is a key of OPTIONS, SS_OPTIONS, LB_OPTIONS or RAY_OPTIONS (or the RT_OPT_* number)."""
         opt = _option(name)
         _check("rt_set_option", lib().rt_set_option(self._h, opt, float(value)), self._err)
 
@@ -373,6 +396,23 @@ class Context:
         _check("rt_render_aov_async",
                lib().rt_render_aov_async(self._h, ctypes.byref(frame), ctypes.byref(aov), stream or None), self._err)
 
+    def trace_rays(self, rays, t: bool = True, id: bool = True, n: bool = True) -> dict:
+        """rt_trace_rays: the closest hit of each ray of the (N, 6) array
+        [Ox Oy Oz Dx Dy Dz] (the direction as given: t is in units of |D|).
+        Returns the requested planes: "t" (N,) float32, "id" (N,) int32 (file
+        index), "n" (N, 3) float32; a miss is -1, -1, (0, 0, 0)."""
+        r, out, aov = _ray_planes(rays, t, id, n)
+        _check("rt_trace_rays", lib().rt_trace_rays(self._h, r.ctypes.data, r.shape[0], ctypes.byref(aov)), self._err)
+        return out
+
+    def trace_rays_async(self, rays_dev_ptr: int, count: int, t_dev_ptr: int = 0, id_dev_ptr: int = 0,
+                         n_dev_ptr: int = 0, stream: int = 0):
+        """rt_trace_rays_async: device pointers to `count` rays and to the planes (0: not requested),
+        enqueued on `stream`."""
+        aov = Aov(t_dev_ptr or None, id_dev_ptr or None, n_dev_ptr or None)
+        _check("rt_trace_rays_async", lib().rt_trace_rays_async(self._h, rays_dev_ptr or None, int(count),
+                                                                ctypes.byref(aov), stream or None), self._err)
+
     def stats(self) -> Stats:
         s = Stats()
         _check("rt_last_stats", lib().rt_last_stats(self._h, ctypes.byref(s)))
@@ -455,6 +495,13 @@ class CpuContext:
         """rt_cpu_render_aov: as Context.render_aov, on host threads (the same bits)."""
         out, aov = _aov_planes(frame, t, id, n)
         _check("rt_cpu_render_aov", lib().rt_cpu_render_aov(self._h, ctypes.byref(frame), ctypes.byref(aov)),
+               self._err)
+        return out
+
+    def trace_rays(self, rays, t: bool = True, id: bool = True, n: bool = True) -> dict:
+        """rt_cpu_trace_rays: as Context.trace_rays, on host threads (the same bits)."""
+        r, out, aov = _ray_planes(rays, t, id, n)
+        _check("rt_cpu_trace_rays", lib().rt_cpu_trace_rays(self._h, r.ctypes.data, r.shape[0], ctypes.byref(aov)),
                self._err)
         return out
 
@@ -553,3 +600,10 @@ class CScene:
         With supersampling they are those of the s W x s H sample grid."""
         f = self._frame()
         return self._ctx.render_aov(f)
+
+    def LancerListeDeRayons(self, rays) -> dict:
+        """The closest hits of the caller's own rays (not in the reference):
+        (N, 6) [Ox Oy Oz Dx Dy Dz] -> {"t", "id", "n"} as Context.trace_rays
+        returns them; the resolution and the supersampling play no part."""
+        self._prepared()
+        return self._ctx.trace_rays(rays)
