@@ -351,6 +351,49 @@ int rt_trace_rays(rt_ctx*, const float* rays, int64_t n, const rt_aov* out);    
 int rt_trace_rays_async(rt_ctx*, const float* dev_rays, int64_t n, const rt_aov* dev_out, void* hip_stream);
 int rt_cpu_trace_rays(rt_ctx*, const float* rays, int64_t n, const rt_aov* out);        /* CPU backend */
 
+/* Shadow-filter (occlusion) queries of arbitrary segments — an addition
+ * within ABI 8 (rt_abi_version() stays 8; test for RT_HAS_FILTER_RAYS): "how
+ * much light gets from A to B", the any-hit half of the ray queries, as
+ * CScene::ObtenirFiltreDeSurface (Scene.cpp:1842-1861) computes it for a
+ * shadow ray: for area lights, ambient occlusion, visibility between agents.
+ * Input.  segs: n records of 6 floats [Px Py Pz Lx Ly Lz] (a C-order (n, 6)
+ * float32 array).  The segment runs from P to P + L; L is the UNNORMALISED
+ * vector, exactly the LumiereRayon the reference hands to that function.
+ * Output.  filter: n x 3 float32.
+ * Definition, one float32 operation per step:
+ *   dist = sqrtf((Lx*Lx + Ly*Ly) + Lz*Lz);  inv = 1.0f / dist;
+ *   D = (Lx*inv, Ly*inv, Lz*inv);  F = (1, 1, 1)
+ *   for every surface i in file order:  t_i = Intersection(P, D)
+ *       if (t_i > EPSILON && t_i < dist)  F *= colour_i * Kt_i
+ * (componentwise; colour * Kt first).  White when nothing is in the way,
+ * exactly zero behind an opaque surface, a tint behind translucent ones.  No
+ * special cases: a zero, tiny, huge or non-finite L gives whatever this
+ * arithmetic gives (usually no comparison holds: white), a NaN stays a NaN.
+ * Lights, camera, bounce depth and background play no part.
+ * rt_filter_rays is synchronous; each of its two pointers is independently a
+ * host or a device pointer.  rt_last_stats afterwards: kernel
+ * ("rt_filter_kernel<0>": the file-order product, or any-hit tests of every
+ * opaque surface; "rt_filter_kernel<1>": the triangles through a segment
+ * any-hit walk of the exact BVH, csrc/rt_filter.h), kernel_ms, shadow_rays =
+ * n, everything else 0.  <1> runs when the scene has the BVH (as for
+ * rt_trace_rays), RT_OPT_BVH is 1 and every factor colour * Kt is finite and
+ * >= +0; the same bits either way.
+ * rt_filter_rays_async takes device pointers only and enqueues one kernel on
+ * `hip_stream`: it allocates nothing, builds nothing and reads or writes no
+ * device state of the context besides the uploaded scene, so it can be
+ * recorded into a hipGraph capture on a context that never rendered; the
+ * stream rules are rt_trace_rays_async's.  Device pointers must be 8-byte
+ * aligned.
+ * RT_OK and nothing written: n == 0.  RT_E_ARG: n < 0 or n > INT32_MAX, a NULL
+ * segs / filter, a misaligned device pointer, a host pointer given to
+ * rt_filter_rays_async.  RT_E_STATE: before rt_upload_scene, or on the other
+ * backend's context (rt_cpu_filter_rays is the CPU backend's: host pointers,
+ * the same bits). */
+#define RT_HAS_FILTER_RAYS 1
+int rt_filter_rays(rt_ctx*, const float* segs, int64_t n, float* filter);                       /* sync; host or device ptrs */
+int rt_filter_rays_async(rt_ctx*, const float* dev_segs, int64_t n, float* dev_filter, void* hip_stream);
+int rt_cpu_filter_rays(rt_ctx*, const float* segs, int64_t n, float* filter);                   /* CPU backend */
+
 /* ABI 4: context options.  A/B and test switches and tuning knobs; no option
  * changes a single bit of any image.  Upload options take effect at the next
  * rt_upload_scene, launch options at the next render.                      */

@@ -23,6 +23,10 @@ int cpu_render_aov(const void* handle, int threads, const rt_frame* f, int rows,
 // null; a miss is -1, -1, 0): rt_rays_kernel's values bit for bit.
 int cpu_trace_rays(const void* handle, int threads, const float* rays, int64_t n, float* t, int32_t* id, float* nrm,
                    double* ms);
+// Shadow-filter queries of n arbitrary segments (rt.h rt_filter_rays: 6 floats
+// per segment, P then the unnormalised L; 3 floats out per segment):
+// rt_filter_kernel's values bit for bit.
+int cpu_filter_rays(const void* handle, int threads, const float* segs, int64_t n, float* filter, double* ms);
 // The supersampling resolve (rt_resolve.h resolve_px, the HIP kernel's own
 // arithmetic): rows_out rows of width / s pixels from their packed sample
 // rows; either output may be null.  *ms = wall time.

@@ -46,6 +46,7 @@
 #include "rt_shade.h"
 #include "rt_bvh.h"
 #include "rt_rays.h"
+#include "rt_filter.h"
 #include "rt_wavefront.h"
 #include "rt_resolve.h"
 #include "rt_scenehost.h"  // scene_host_build, lb_plan; RT_BVH_MIN_TRIANGLES
@@ -3774,6 +3775,126 @@ RT_EXPORT int rt_cpu_trace_rays(rt_ctx* c, const float* rays, int64_t n, const r
     c->last.kernel_ms = (float)ms;
     c->last.bounce_rays = (uint64_t)n;
     std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_trace_rays");
+    return rc;
+}
+
+// ---- shadow-filter queries of arbitrary segments (rt.h rt_filter_rays*, rt_filter.h)
+// The checks every filter entry point shares (rays_check's rules).
+static int filter_check(rt_ctx* c, const float* segs, int64_t n, const float* out, bool* go)
+{
+    *go = false;
+    if (int rc = check_uploaded(c, "rt_filter_rays")) return rc;
+    if (n < 0 || n > INT32_MAX) {
+        c->err = "rt_filter_rays: the segment count must be 0 .. INT32_MAX";
+        return RT_E_ARG;
+    }
+    if (n == 0) return RT_OK;
+    if (!segs || !out) {
+        c->err = "rt_filter_rays: no segments or no output";
+        return RT_E_ARG;
+    }
+    *go = true;
+    return RT_OK;
+}
+
+static int filter_aligned(rt_ctx* c, const void* p)
+{
+    if (((uintptr_t)p & 7u) == 0) return RT_OK;
+    c->err = "rt_filter_rays: device pointers must be 8-byte aligned";
+    return RT_E_ARG;
+}
+
+// The any-hit walk needs the tree and factors that are all finite and >= +0
+// (rt_filter.h); else the file-order product.
+static bool filter_bvh_on(const rt_ctx* c) { return rays_bvh(c) && c->shadow_split; }
+
+// n segments into dev_out on st: one kernel, no state of the context.
+static int launch_filter(rt_ctx* c, const float* d_segs, int n, float* d_out, hipStream_t st)
+{
+    const bool bvh = filter_bvh_on(c);
+    SceneDev S = scene_dev(c, c->cam, false, false);
+    const float2* segs = reinterpret_cast<const float2*>(d_segs);
+    int depth = c->bvh_depth;
+    void* args[] = {&S, &segs, &n, &d_out, &depth};
+    const void* k = bvh ? (const void*)&rt_filter_kernel<1> : (const void*)&rt_filter_kernel<0>;
+    const unsigned lds = bvh ? (unsigned)filter_lds_bytes(c->bvh_depth) : 0u;
+    HIP_TRY(c, hipLaunchKernel(k, dim3((unsigned)(((int64_t)n + 63) / 64)), dim3(64), args, lds, st));
+    return RT_OK;
+}
+
+RT_EXPORT int rt_filter_rays(rt_ctx* c, const float* segs, int64_t n, float* filter)
+{
+    if (!c) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    bool go;
+    if (int rc = filter_check(c, segs, n, filter, &go)) return rc;
+    if (!go) return RT_OK;
+    if (int rc = sync_begin(c)) return rc;
+    // the scratch: a host segment array first, then the host output
+    const bool segs_host = !is_device_ptr(segs);
+    const size_t sbytes = (size_t)n * 6 * sizeof(float), obytes = (size_t)n * 3 * sizeof(float);
+    SyncOut o;
+    if (segs_host) o.need = (sbytes + 255) / 256 * 256;
+    o.add(filter, (obytes + 255) / 256 * 256);
+    if (!segs_host)
+        if (int rc = filter_aligned(c, segs)) return rc;
+    if (!o.host[0])
+        if (int rc = filter_aligned(c, filter)) return rc;
+    if (int rc = o.place(c)) return rc;
+    const float* d_segs = segs;
+    if (segs_host) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_scratch, segs, sbytes, hipMemcpyHostToDevice, c->stream));
+        d_segs = (const float*)c->d_scratch;
+    }
+    c->last = rt_stats{};
+    std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_filter_kernel<%d>", filter_bvh_on(c) ? 1 : 0);
+    c->last.shadow_rays = (uint64_t)n;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    if (int rc = launch_filter(c, d_segs, (int)n, (float*)o.target[0], c->stream)) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    if (int rc = o.copy_back(c, 0, obytes)) return rc;
+    static const rt_frame no_frame{};  // (no RT_FLAG_STATS)
+    return finish_sync(c, &no_frame, c->stream, true);
+}
+
+RT_EXPORT int rt_filter_rays_async(rt_ctx* c, const float* dev_segs, int64_t n, float* dev_filter, void* stream)
+{
+    if (!c) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    bool go;
+    if (int rc = filter_check(c, dev_segs, n, dev_filter, &go)) return rc;
+    if (!go) return RT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const void* const ptr[2] = {dev_segs, dev_filter};
+    for (const void* p : ptr) {
+        if (!is_device_ptr(p)) {
+            c->err = "rt_filter_rays_async takes device pointers";
+            return RT_E_ARG;
+        }
+        if (int rc = filter_aligned(c, p)) return rc;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    bool capturing = false;
+    if (int rc = stream_capturing(c, st, &capturing)) return rc;
+    if (int rc = launch_filter(c, dev_segs, (int)n, dev_filter, st)) return rc;
+    // (host bookkeeping only: an upload syncs st, or keeps what a graph references)
+    enqueued(c, st, capturing, nullptr);
+    return RT_OK;
+}
+
+RT_EXPORT int rt_cpu_filter_rays(rt_ctx* c, const float* segs, int64_t n, float* filter)
+{
+    if (!c) return RT_E_ARG;
+    if (!c->cpu) return needs_cpu(c, "rt_cpu_filter_rays");
+    bool go;
+    if (int rc = filter_check(c, segs, n, filter, &go)) return rc;
+    if (!go) return RT_OK;
+    c->last = rt_stats{};
+    double ms = 0.0;
+    const int rc = cpu_filter_rays(c->cpu_scene, c->cpu_threads, segs, n, filter, &ms);
+    c->last.kernel_ms = (float)ms;
+    c->last.shadow_rays = (uint64_t)n;
+    std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_filter_rays");
     return rc;
 }
 

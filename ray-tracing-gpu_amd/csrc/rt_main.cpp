@@ -4,6 +4,7 @@
 //             [--device first] [--bands] [-n frames] [-s]
 //             [--gather rccl|host] [--backend hip|cpu] [--threads N]
 //             [--ssaa N] [--aov PREFIX] [--rays IN.npy --hits PREFIX [--ray-bvh]]
+//             [--segments IN.npy --filters OUT.npy [--ray-bvh]]
 //
 // Kept from Main.cpp:51-199: argv[1] is the scene file, -x / -y set the
 // resolution (default 512x256, Var.cpp:4-5), the same [ETAT]/[ERREUR] log
@@ -46,6 +47,10 @@
 // by --aov's writer; on either backend, one GPU; --ray-bvh sets
 // RT_OPT_RAY_BVH for the upload.  The frame itself is then rendered only when
 // -o names a file.
+// --segments IN.npy --filters OUT.npy asks for the shadow filter of the
+// caller's own segments (rt_filter_rays / rt_cpu_filter_rays): IN.npy is read
+// by --rays' reader as (N, 6) [Px Py Pz Lx Ly Lz] (from P to P + L), OUT.npy
+// is float32 (N, 3); the same rules as --rays, with which it can be combined.
 #include <hip/hip_runtime_api.h>
 
 #include <dlfcn.h>
@@ -233,6 +238,24 @@ static int write_hits(rt_ctx* c, bool cpu, const std::vector<float>& rays, const
     if (write_npy(p + "_t.npy", "<f4", (int)n, 0, 1, t.data(), n * 4)) return fail("fopen", -1, (p + "_t.npy").c_str());
     if (write_npy(p + "_id.npy", "<i4", (int)n, 0, 1, id.data(), n * 4)) return fail("fopen", -1, (p + "_id.npy").c_str());
     if (write_npy(p + "_n.npy", "<f4", (int)n, 3, 1, nrm.data(), n * 12)) return fail("fopen", -1, (p + "_n.npy").c_str());
+    return 0;
+}
+
+// --segments / --filters: the shadow filters of the file's segments from context c (either backend).
+static int write_filters(rt_ctx* c, bool cpu, const std::vector<float>& segs, const char* path)
+{
+    const uint16_t probe = 1;
+    if (*(const unsigned char*)&probe != 1) return fail("--filters", RT_E_UNSUPPORTED, "little-endian hosts only");
+    const size_t n = segs.size() / 6;
+    std::vector<float> f(n * 3);
+    const int rc = n == 0 ? 0
+                   : cpu  ? rt_cpu_filter_rays(c, segs.data(), (int64_t)n, f.data())
+                          : rt_filter_rays(c, segs.data(), (int64_t)n, f.data());
+    if (rc) return fail("rt_filter_rays", rc, rt_last_error(c));
+    rt_stats st;
+    rt_last_stats(c, &st);
+    if (n) std::printf("[ETAT]: %zu segments, %s, %.3f ms\n", n, st.kernel, st.kernel_ms);
+    if (write_npy(path, "<f4", (int)n, 3, 1, f.data(), n * 12)) return fail("fopen", -1, path);
     return 0;
 }
 
@@ -473,6 +496,8 @@ int main(int argc, char** argv)
     const char* rays_in = nullptr;
     const char* hits = nullptr;
     bool ray_bvh = false;
+    const char* segs_in = nullptr;
+    const char* filters = nullptr;
     for (int i = 2; i < argc; ++i) {
         if (argv[i][0] != '-') continue;
         auto next = [&](int& v) {
@@ -505,6 +530,16 @@ int main(int argc, char** argv)
         if (std::strcmp(argv[i], "--hits") == 0) {
             if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--hits needs a file prefix");
             hits = argv[++i];
+            continue;
+        }
+        if (std::strcmp(argv[i], "--segments") == 0) {
+            if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--segments needs a .npy file");
+            segs_in = argv[++i];
+            continue;
+        }
+        if (std::strcmp(argv[i], "--filters") == 0) {
+            if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--filters needs a .npy file to write");
+            filters = argv[++i];
             continue;
         }
         if (std::strcmp(argv[i], "--ray-bvh") == 0) {
@@ -564,11 +599,22 @@ int main(int argc, char** argv)
     if (rays_in && (gpus != 1 || bands || gather == 1))
         return fail("arguments", RT_E_ARG,
                     "--rays traces on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
-    if (ray_bvh && !rays_in) return fail("arguments", RT_E_ARG, "--ray-bvh goes with --rays");
+    if ((segs_in != nullptr) != (filters != nullptr))
+        return fail("arguments", RT_E_ARG, "--segments IN.npy and --filters OUT.npy go together");
+    if (segs_in && (gpus != 1 || bands || gather == 1))
+        return fail("arguments", RT_E_ARG,
+                    "--segments filters on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
+    if (ray_bvh && !rays_in && !segs_in) return fail("arguments", RT_E_ARG, "--ray-bvh goes with --rays or --segments");
     std::vector<float> rays;
     if (rays_in) {
         std::string why;
         if (!read_rays_npy(rays_in, rays, why)) return fail("--rays", RT_E_ARG, (std::string(rays_in) + ": " + why).c_str());
+    }
+    std::vector<float> segs;
+    if (segs_in) {
+        std::string why;
+        if (!read_rays_npy(segs_in, segs, why))
+            return fail("--segments", RT_E_ARG, (std::string(segs_in) + ": " + why).c_str());
     }
     if (((W - 1) & W) || ((H - 1) & H))
         std::fprintf(stderr, "[ATTENTION]: Resolution %dx%d n'est pas une puissance de deux "
@@ -588,7 +634,7 @@ int main(int argc, char** argv)
     rt_scene_get_frame(scene, &frame);
     if (stats) frame.flags |= RT_FLAG_STATS;
 
-    if (rays_in) {  // ray queries: one context of either backend; the frame only for -o
+    if (rays_in || segs_in) {  // ray / filter queries: one context of either backend; the frame only for -o
         rt_ctx* c = nullptr;
         if (cpu) {
             if ((rc = rt_create_cpu(threads, &c))) return fail("rt_create_cpu", rc, "");
@@ -599,8 +645,14 @@ int main(int argc, char** argv)
         }
         if (ray_bvh && (rc = rt_set_option(c, RT_OPT_RAY_BVH, 1.0))) return fail("rt_set_option", rc, rt_last_error(c));
         if ((rc = rt_upload_scene(c, &flat))) return fail("rt_upload_scene", rc, rt_last_error(c));
-        std::printf("[ETAT]: Lancer de rayons (%zu rayons de %s)...\n", rays.size() / 6, rays_in);
-        if (write_hits(c, cpu, rays, hits)) return 1;
+        if (rays_in) {
+            std::printf("[ETAT]: Lancer de rayons (%zu rayons de %s)...\n", rays.size() / 6, rays_in);
+            if (write_hits(c, cpu, rays, hits)) return 1;
+        }
+        if (segs_in) {
+            std::printf("[ETAT]: Filtres d'ombre (%zu segments de %s)...\n", segs.size() / 6, segs_in);
+            if (write_filters(c, cpu, segs, filters)) return 1;
+        }
         if (out) {
             std::vector<uint8_t> img((size_t)W * H * 4);
             rc = cpu ? (ssaa > 1 ? rt_cpu_render_ss(c, &frame, ssaa, img.data()) : rt_cpu_render(c, &frame, img.data()))

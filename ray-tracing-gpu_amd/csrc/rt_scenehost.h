@@ -315,6 +315,17 @@ inline void scene_host_bvh(SceneHost& H, bool ray_bvh = false)
         for (int i = 0; i < n; ++i)
             if (!is_tri[(size_t)i]) H.skey[(size_t)i] = nb++;
         H.nbin_half = nb;
+        // word 10 of a leaf record ([2].z, 0 in tri[]): int 1 for a translucent
+        // triangle — rt_filter_kernel<1>'s any-hit walk alone reads it
+        for (int i = 0; i < H.n_tri; ++i) {
+            float4& c = H.bvh.tris[3 * (size_t)i + 2];
+            int fi;
+            std::memcpy(&fi, &c.y, sizeof fi);
+            if (!(fi >= 0 && fi < n)) continue;
+            const float* o = &H.geom[16 * (size_t)fi];
+            const int translucent = !(o[13] == 0.0f && o[14] == 0.0f && o[15] == 0.0f);
+            std::memcpy(&c.z, &translucent, sizeof translucent);
+        }
         H.has_bvh = true;
     } else {
         H.bvh = BvhBuilt{};

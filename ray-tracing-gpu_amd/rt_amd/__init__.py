@@ -130,6 +130,9 @@ SIGNATURES = {
     "rt_trace_rays": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(Aov)]),
     "rt_trace_rays_async": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(Aov), _VP]),
     "rt_cpu_trace_rays": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(Aov)]),
+    "rt_filter_rays": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP]),
+    "rt_filter_rays_async": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP, _VP]),
+    "rt_cpu_filter_rays": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP]),
     "rt_upload_scene": (ctypes.c_int, [_VP, ctypes.POINTER(SceneFlat)]),
     "rt_render": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
     "rt_render_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
@@ -202,6 +205,14 @@ def _ray_planes(rays, t: bool, id: bool, n: bool):
         out["n"] = np.zeros((count, 3), np.float32)
     aov = Aov(*(out[k].ctypes.data if k in out else None for k in ("t", "id", "n")))
     return r, out, aov
+
+
+def _segments(segs):
+    """The (N, 6) float32 segment array and the (N, 3) float32 array its filters go to."""
+    s = np.ascontiguousarray(segs, np.float32)
+    if s.ndim != 2 or s.shape[1] != 6:
+        raise ValueError("segs: an (N, 6) array [Px Py Pz Lx Ly Lz]")
+    return s, np.zeros((s.shape[0], 3), np.float32)
 
 
 def _option(name) -> int:
@@ -413,6 +424,21 @@ class Context:
         _check("rt_trace_rays_async", lib().rt_trace_rays_async(self._h, rays_dev_ptr or None, int(count),
                                                                 ctypes.byref(aov), stream or None), self._err)
 
+    def filter_rays(self, segs) -> np.ndarray:
+        """rt_filter_rays: the shadow filter of each segment of the (N, 6) array
+        [Px Py Pz Lx Ly Lz] (from P to P + L, L unnormalised) -> (N, 3) float32:
+        white where nothing is in the way, zero behind an opaque surface, the
+        file-order product of colour x Kt behind translucent ones."""
+        s, out = _segments(segs)
+        _check("rt_filter_rays", lib().rt_filter_rays(self._h, s.ctypes.data, s.shape[0], out.ctypes.data), self._err)
+        return out
+
+    def filter_rays_async(self, segs_dev_ptr: int, count: int, filter_dev_ptr: int, stream: int = 0):
+        """rt_filter_rays_async: device pointers to `count` segments and to their 3 x `count` floats,
+        enqueued on `stream`."""
+        _check("rt_filter_rays_async", lib().rt_filter_rays_async(self._h, segs_dev_ptr or None, int(count),
+                                                                  filter_dev_ptr or None, stream or None), self._err)
+
     def stats(self) -> Stats:
         s = Stats()
         _check("rt_last_stats", lib().rt_last_stats(self._h, ctypes.byref(s)))
@@ -502,6 +528,13 @@ class CpuContext:
         """rt_cpu_trace_rays: as Context.trace_rays, on host threads (the same bits)."""
         r, out, aov = _ray_planes(rays, t, id, n)
         _check("rt_cpu_trace_rays", lib().rt_cpu_trace_rays(self._h, r.ctypes.data, r.shape[0], ctypes.byref(aov)),
+               self._err)
+        return out
+
+    def filter_rays(self, segs) -> np.ndarray:
+        """rt_cpu_filter_rays: as Context.filter_rays, on host threads (the same bits)."""
+        s, out = _segments(segs)
+        _check("rt_cpu_filter_rays", lib().rt_cpu_filter_rays(self._h, s.ctypes.data, s.shape[0], out.ctypes.data),
                self._err)
         return out
 
@@ -607,3 +640,10 @@ class CScene:
         returns them; the resolution and the supersampling play no part."""
         self._prepared()
         return self._ctx.trace_rays(rays)
+
+    def LancerListeDeRayonsOmbre(self, segs) -> np.ndarray:
+        """ObtenirFiltreDeSurface for the caller's own segments (not a verb of
+        the reference): (N, 6) [Px Py Pz Lx Ly Lz] -> (N, 3) float32 as
+        Context.filter_rays returns them."""
+        self._prepared()
+        return self._ctx.filter_rays(segs)
