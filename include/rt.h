@@ -394,6 +394,54 @@ int rt_filter_rays(rt_ctx*, const float* segs, int64_t n, float* filter);       
 int rt_filter_rays_async(rt_ctx*, const float* dev_segs, int64_t n, float* dev_filter, void* hip_stream);
 int rt_cpu_filter_rays(rt_ctx*, const float* segs, int64_t n, float* filter);                   /* CPU backend */
 
+/* Radiance queries of arbitrary rays — an addition within ABI 8
+ * (rt_abi_version() stays 8; test for RT_HAS_SHADE_RAYS): "what colour comes
+ * along this ray", the third piece beside the closest-hit and the filter
+ * queries, for cameras the pinhole frame cannot express (fisheye, panorama,
+ * orthographic, depth of field), reflection and light probes, foveated or
+ * re-projected sample patterns, sensors.
+ * Input.  rays: n records of 6 floats [Ox Oy Oz Dx Dy Dz] (a C-order (n, 6)
+ * float32 array).  D is used AS GIVEN, not normalised, as in rt_trace_rays.
+ * params: an rt_frame of which max_bounces, min_energy, scene_ior and
+ * background are read; its camera, resolution, slab and band fields are
+ * ignored, and so is RT_FLAG_STATS in its flags.
+ * Output.  rgb: n x 3 float32.
+ * Definition: CScene::ObtenirCouleur (Scene.cpp:1705-1826, with the commented
+ * reflect / refract recursion re-enabled below max_bounces, as for a render)
+ * of a CRayon with origin O, direction D, energy 1, 0 bounces and IOR 1 — the
+ * state the pixel loop gives a camera ray: the background on a miss, else
+ * ambient + shadow-filtered Lambert and Phong of every light, + Kr x the
+ * reflected ray's colour + Kt x the refracted ray's.  The float image of a
+ * frame therefore equals this query of the frame's camera rays (bit for bit
+ * on the CPU backend; on the GPU within the renders' own allowance for powf
+ * on materials with a shininess).  No special cases: a zero or non-finite O
+ * or D gives whatever this arithmetic gives, usually the background.
+ * rt_shade_rays is synchronous; each of its two array pointers is
+ * independently a host or a device pointer.  rt_last_stats afterwards: kernel
+ * ("rt_shade_rays_kernel<MAXD,1,flags>", csrc/rt_shaderays.h: MAXD the
+ * smallest compiled bounce stack of 0 1 2 3 5 8 16 32 that covers the
+ * reachable depth; flags 16 every surface per ray, 21 / 22 depth 0 with the
+ * light buffer, 277 / 278 the exact BVH for every ray of the tree and the
+ * light buffer — when the scene has the BVH as for rt_trace_rays,
+ * RT_OPT_RAY_BVH included; the same bits whichever runs), kernel_ms,
+ * primary_rays = n, stack_depth, everything else 0.
+ * rt_shade_rays_async takes device pointers only and enqueues one kernel on
+ * `hip_stream`: it allocates nothing, builds nothing and reads or writes no
+ * device state of the context besides the uploaded scene (its light buffer
+ * and BVH included), so it can be recorded into a hipGraph capture on a
+ * context that never rendered; the stream rules are rt_trace_rays_async's.
+ * Device pointers must be 8-byte aligned.  `params` is read during the call.
+ * RT_OK and nothing written: n == 0.  RT_E_ARG: a NULL params, n < 0 or n >
+ * INT32_MAX, a NULL rays / rgb, a misaligned device pointer, a host pointer
+ * given to rt_shade_rays_async.  RT_E_STATE: before rt_upload_scene, or on the
+ * other backend's context (rt_cpu_shade_rays is the CPU backend's: host
+ * pointers, the same bits).  RT_E_UNSUPPORTED: the reachable bounce depth
+ * exceeds the deepest compiled stack (32), as for a render. */
+#define RT_HAS_SHADE_RAYS 1
+int rt_shade_rays(rt_ctx*, const rt_frame* params, const float* rays, int64_t n, float* rgb);      /* sync; host or device ptrs */
+int rt_shade_rays_async(rt_ctx*, const rt_frame* params, const float* dev_rays, int64_t n, float* dev_rgb, void* hip_stream);
+int rt_cpu_shade_rays(rt_ctx*, const rt_frame* params, const float* rays, int64_t n, float* rgb);  /* CPU backend */
+
 /* ABI 4: context options.  A/B and test switches and tuning knobs; no option
  * changes a single bit of any image.  Upload options take effect at the next
  * rt_upload_scene, launch options at the next render.                      */

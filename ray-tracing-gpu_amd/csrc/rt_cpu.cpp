@@ -522,6 +522,42 @@ int cpu_filter_rays(const void* handle, int threads, const float* segs, int64_t 
     return RT_OK;
 }
 
+// Radiance queries (rt.h rt_shade_rays): the frames' own trace() per ray —
+// a camera ray's state (energy 1, 0 bounces, IOR 1) with the caller's O and
+// D as given —, chunked like cpu_trace_rays.  Of f, trace() reads
+// max_bounces, min_energy, scene_ior and background.
+int cpu_shade_rays(const void* handle, int threads, const rt_frame* f, const float* rays, int64_t n, float* out,
+                   double* ms)
+{
+    using namespace cpu;
+    const Scene& S = *static_cast<const Scene*>(handle);
+    const auto t0 = std::chrono::steady_clock::now();
+    std::atomic<int64_t> next{0};
+    constexpr int64_t kChunk = 256;
+    auto work = [&]() {
+        for (;;) {
+            const int64_t i0 = next.fetch_add(kChunk);
+            if (i0 >= n) return;
+            for (int64_t i = i0; i < std::min(n, i0 + kChunk); ++i) {
+                const float* r = rays + 6 * (size_t)i;
+                const Ray ray{make3(r[0], r[1], r[2]), make3(r[3], r[4], r[5]), 1.0f, 1.0f, 0};
+                const Color c = trace(S, *f, ray);
+                out[3 * i] = c.r;
+                out[3 * i + 1] = c.g;
+                out[3 * i + 2] = c.b;
+            }
+        }
+    };
+    int64_t k = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());
+    k = std::max<int64_t>(1, std::min(k, (n + kChunk - 1) / kChunk));
+    std::vector<std::thread> pool;
+    for (int64_t i = 1; i < k; ++i) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
 void cpu_resolve(const float* samples, int width, int s, int rows_out, uint8_t* rgba, float* rgb, double* ms)
 {
     const auto t0 = std::chrono::steady_clock::now();

@@ -27,6 +27,12 @@ int cpu_trace_rays(const void* handle, int threads, const float* rays, int64_t n
 // per segment, P then the unnormalised L; 3 floats out per segment):
 // rt_filter_kernel's values bit for bit.
 int cpu_filter_rays(const void* handle, int threads, const float* segs, int64_t n, float* filter, double* ms);
+// Radiance queries of n arbitrary rays (rt.h rt_shade_rays: 6 floats per ray,
+// O then D as given; 3 floats out per ray; f carries max_bounces, min_energy,
+// scene_ior and background): rt_shade_rays_kernel's values (bit for bit but
+// for powf on materials with a shininess, as for a render).
+int cpu_shade_rays(const void* handle, int threads, const rt_frame* f, const float* rays, int64_t n, float* rgb,
+                   double* ms);
 // The supersampling resolve (rt_resolve.h resolve_px, the HIP kernel's own
 // arithmetic): rows_out rows of width / s pixels from their packed sample
 // rows; either output may be null.  *ms = wall time.

@@ -73,6 +73,8 @@ struct Refr {
 // kWf0 (MAXD 0, the wavefront's level 0, rt_wavefront.h): a hit
 // that spawns children writes a node record and its child rays instead of
 // its colour (deferred: rt_wf_fold writes the pixel).
+// kRayQuery (rt_shaderays.h): O, D are the caller's, not a camera ray's —
+// the first search is a bounce ray's (tile is unused); nothing else differs.
 template <int MAXD, int LB, int WAVE>
 __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, Counters& cnt, bool live, int tile,
                           unsigned pix, bool& deferred, unsigned chunk)
@@ -81,7 +83,13 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
     if constexpr (MAXD == 0) {
         float t;
         RT_MARK(cnt, 0);
-        const int idx = closest_hit_primary<camera_ray_bits(WAVE)>(S, O, D, t, cnt, tile);
+        int idx;
+        if constexpr (!is_ray_query(WAVE))
+            idx = closest_hit_primary<camera_ray_bits(WAVE)>(S, O, D, t, cnt, tile);
+        else if constexpr (has_bvh(WAVE))  // kRayQuery: the caller's ray, searched like a bounce ray
+            idx = closest_hit_bvh(S, O, D, t, cnt);
+        else
+            idx = closest_hit<false>(S, O, D, t, cnt);
         RT_MARK(cnt, 1);
         // Lanes that miss (or lie outside the frame) stay in step through the
         // shading so the wave stays whole for wave-level shadow culling.
@@ -125,7 +133,7 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
         for (int lv = 0;; ++lv) {
             float t;
             int idx;
-            if (lv == 0)
+            if (!is_ray_query(WAVE) && lv == 0)
                 idx = closest_hit_primary<camera_ray_bits(WAVE)>(S, O, D, t, cnt, tile);
             else if constexpr (has_bvh(WAVE))  // bounce rays through the BVH (rt_bvh.h)
                 idx = closest_hit_bvh(S, O, D, t, cnt);
@@ -172,7 +180,7 @@ __device__ Color radiance(const SceneDev& S, const FrameDev& F, Vec3 O, Vec3 D, 
         int sp = 0;
         float rior = 1.0f, energy = 1.0f;
         Color ret{0.f, 0.f, 0.f};
-        bool trace = true, camera_ray = true;
+        bool trace = true, camera_ray = !is_ray_query(WAVE);  // kRayQuery: no ray of the tree is a camera ray
         for (;;) {
             if (trace) {
                 float t;
@@ -941,6 +949,7 @@ __global__ __launch_bounds__(64) void rt_bvh_wave_kernel(const SceneDev S, const
 }  // namespace rt
 
 #include "rt_aov.h"  // rt_aov_kernel (needs tile_of_block above)
+#include "rt_shaderays.h"  // rt_shade_rays_kernel (needs radiance and waves_per_eu above)
 
 // ===================================================================== host
 using namespace rt;
@@ -3895,6 +3904,165 @@ RT_EXPORT int rt_cpu_filter_rays(rt_ctx* c, const float* segs, int64_t n, float*
     c->last.kernel_ms = (float)ms;
     c->last.shadow_rays = (uint64_t)n;
     std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_filter_rays");
+    return rc;
+}
+
+// ---- radiance queries of arbitrary rays (rt.h rt_shade_rays*, rt_shaderays.h)
+#define RT_V(M, L, F) \
+    {{M, L, F}, {(const void*)&rt_shade_rays_kernel<M, L, F>}, kernel_name("rt_shade_rays_kernel", M, L, F)},
+static const KernelRow<1> kShadeRaysKernels[] = {RT_SHADE_RAYS_VARIANTS};
+#undef RT_V
+
+// The checks every shade entry point shares (filter_check's rules, and the
+// frame that carries the parameters).
+static int shade_rays_check(rt_ctx* c, const rt_frame* f, const float* rays, int64_t n, const float* out, bool* go)
+{
+    *go = false;
+    if (int rc = check_uploaded(c, "rt_shade_rays")) return rc;
+    if (!f) {
+        c->err = "rt_shade_rays: no rt_frame (max_bounces, min_energy, scene_ior, background)";
+        return RT_E_ARG;
+    }
+    if (n < 0 || n > INT32_MAX) {
+        c->err = "rt_shade_rays: the ray count must be 0 .. INT32_MAX";
+        return RT_E_ARG;
+    }
+    if (n == 0) return RT_OK;
+    if (!rays || !out) {
+        c->err = "rt_shade_rays: no rays or no output";
+        return RT_E_ARG;
+    }
+    *go = true;
+    return RT_OK;
+}
+
+static int shade_rays_aligned(rt_ctx* c, const void* p)
+{
+    if (((uintptr_t)p & 7u) == 0) return RT_OK;
+    c->err = "rt_shade_rays: device pointers must be 8-byte aligned";
+    return RT_E_ARG;
+}
+
+// The query's kernel for the parameters of f: select_query_variant's row
+// (k == nullptr: the reachable depth exceeds the compiled stacks).
+static int pick_shade_rays(rt_ctx* c, const rt_frame* f, KernelPick& p)
+{
+    QueryFacts q;
+    q.depth = reachable_depth(c, f);
+    q.n_tri = c->n_tri;
+    q.lbuf = lbuf_on(c);
+    q.bvh = rays_bvh(c);
+    p = KernelPick{};
+    p.v = select_query_variant(q);
+    if (const KernelRow<1>* r = find_row(kShadeRaysKernels, p.v)) {
+        p.k = r->k[0];
+        p.name = &r->name;
+        p.lds = lds_bytes(p.v.flags, c->bvh_depth);
+        return RT_OK;
+    }
+    c->err = "reachable bounce depth " + std::to_string(q.depth) + " exceeds the compiled stack (32)";
+    return RT_E_UNSUPPORTED;
+}
+
+// n rays into d_rgb on st: one kernel, no state of the context besides the
+// uploaded scene (light buffer and BVH included).  c->cam may never have been
+// prepared: its fields are then null, and no query instance reads them
+// (rt_shaderays.h).
+static int launch_shade_rays(rt_ctx* c, const KernelPick& kp, const rt_frame* f, const float* d_rays, int n,
+                             float* d_rgb, hipStream_t st)
+{
+    SceneDev S = scene_dev(c, c->cam, has_light_buf(kp.v.flags), false);
+    FrameDev F{};  // what radiance reads outside kWf0, and nothing of the camera
+    std::memcpy(F.bg, f->background, sizeof F.bg);
+    F.max_bounces = f->max_bounces;
+    F.min_energy = f->min_energy;
+    F.scene_ior = f->scene_ior;
+    const float2* rays = reinterpret_cast<const float2*>(d_rays);
+    void* args[] = {&S, &F, &rays, &n, &d_rgb};
+    HIP_TRY(c, hipLaunchKernel(kp.k, dim3((unsigned)(((int64_t)n + 63) / 64)), dim3(64), args, kp.lds, st));
+    return RT_OK;
+}
+
+RT_EXPORT int rt_shade_rays(rt_ctx* c, const rt_frame* f, const float* rays, int64_t n, float* rgb)
+{
+    if (!c) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    bool go;
+    if (int rc = shade_rays_check(c, f, rays, n, rgb, &go)) return rc;
+    if (!go) return RT_OK;
+    KernelPick kp;
+    if (int rc = pick_shade_rays(c, f, kp)) return rc;
+    if (int rc = sync_begin(c)) return rc;
+    // the scratch: a host ray array first, then the host output
+    const bool rays_host = !is_device_ptr(rays);
+    const size_t rbytes = (size_t)n * 6 * sizeof(float), obytes = (size_t)n * 3 * sizeof(float);
+    SyncOut o;
+    if (rays_host) o.need = (rbytes + 255) / 256 * 256;
+    o.add(rgb, (obytes + 255) / 256 * 256);
+    if (!rays_host)
+        if (int rc = shade_rays_aligned(c, rays)) return rc;
+    if (!o.host[0])
+        if (int rc = shade_rays_aligned(c, rgb)) return rc;
+    if (int rc = o.place(c)) return rc;
+    const float* d_rays = rays;
+    if (rays_host) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_scratch, rays, rbytes, hipMemcpyHostToDevice, c->stream));
+        d_rays = (const float*)c->d_scratch;
+    }
+    c->last = rt_stats{};
+    std::memcpy(c->last.kernel, kp.name->s, sizeof kp.name->s);
+    c->last.primary_rays = (uint64_t)n;
+    c->last.stack_depth = kp.v.maxd;
+    c->last.light_batch = kp.v.lb;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    if (int rc = launch_shade_rays(c, kp, f, d_rays, (int)n, (float*)o.target[0], c->stream)) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    if (int rc = o.copy_back(c, 0, obytes)) return rc;
+    static const rt_frame no_frame{};  // (RT_FLAG_STATS in f->flags is ignored: no counting instances)
+    return finish_sync(c, &no_frame, c->stream, true);
+}
+
+RT_EXPORT int rt_shade_rays_async(rt_ctx* c, const rt_frame* f, const float* dev_rays, int64_t n, float* dev_rgb,
+                                  void* stream)
+{
+    if (!c) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    bool go;
+    if (int rc = shade_rays_check(c, f, dev_rays, n, dev_rgb, &go)) return rc;
+    if (!go) return RT_OK;
+    KernelPick kp;
+    if (int rc = pick_shade_rays(c, f, kp)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const void* const ptr[2] = {dev_rays, dev_rgb};
+    for (const void* p : ptr) {
+        if (!is_device_ptr(p)) {
+            c->err = "rt_shade_rays_async takes device pointers";
+            return RT_E_ARG;
+        }
+        if (int rc = shade_rays_aligned(c, p)) return rc;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    bool capturing = false;
+    if (int rc = stream_capturing(c, st, &capturing)) return rc;
+    if (int rc = launch_shade_rays(c, kp, f, dev_rays, (int)n, dev_rgb, st)) return rc;
+    // (host bookkeeping only: an upload syncs st, or keeps what a graph references)
+    enqueued(c, st, capturing, nullptr);
+    return RT_OK;
+}
+
+RT_EXPORT int rt_cpu_shade_rays(rt_ctx* c, const rt_frame* f, const float* rays, int64_t n, float* rgb)
+{
+    if (!c) return RT_E_ARG;
+    if (!c->cpu) return needs_cpu(c, "rt_cpu_shade_rays");
+    bool go;
+    if (int rc = shade_rays_check(c, f, rays, n, rgb, &go)) return rc;
+    if (!go) return RT_OK;
+    c->last = rt_stats{};
+    double ms = 0.0;
+    const int rc = cpu_shade_rays(c->cpu_scene, c->cpu_threads, f, rays, n, rgb, &ms);
+    c->last.kernel_ms = (float)ms;
+    c->last.primary_rays = (uint64_t)n;
+    std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_shade_rays");
     return rc;
 }
 

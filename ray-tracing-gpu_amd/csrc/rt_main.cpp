@@ -5,6 +5,7 @@
 //             [--gather rccl|host] [--backend hip|cpu] [--threads N]
 //             [--ssaa N] [--aov PREFIX] [--rays IN.npy --hits PREFIX [--ray-bvh]]
 //             [--segments IN.npy --filters OUT.npy [--ray-bvh]]
+//             [--rays IN.npy --colours OUT.npy [-d N] [--ray-bvh]]
 //
 // Kept from Main.cpp:51-199: argv[1] is the scene file, -x / -y set the
 // resolution (default 512x256, Var.cpp:4-5), the same [ETAT]/[ERREUR] log
@@ -51,6 +52,10 @@
 // caller's own segments (rt_filter_rays / rt_cpu_filter_rays): IN.npy is read
 // by --rays' reader as (N, 6) [Px Py Pz Lx Ly Lz] (from P to P + L), OUT.npy
 // is float32 (N, 3); the same rules as --rays, with which it can be combined.
+// --rays IN.npy --colours OUT.npy asks for the colour along the caller's own
+// rays (rt_shade_rays / rt_cpu_shade_rays) with the scene's parameters and
+// -d's bounce depth: OUT.npy is float32 (N, 3).  Alone or beside --hits; the
+// same rules as --hits.
 #include <hip/hip_runtime_api.h>
 
 #include <dlfcn.h>
@@ -256,6 +261,24 @@ static int write_filters(rt_ctx* c, bool cpu, const std::vector<float>& segs, co
     rt_last_stats(c, &st);
     if (n) std::printf("[ETAT]: %zu segments, %s, %.3f ms\n", n, st.kernel, st.kernel_ms);
     if (write_npy(path, "<f4", (int)n, 3, 1, f.data(), n * 12)) return fail("fopen", -1, path);
+    return 0;
+}
+
+// --rays / --colours: the colours along the file's rays from context c (either backend).
+static int write_colours(rt_ctx* c, bool cpu, const rt_frame& frame, const std::vector<float>& rays, const char* path)
+{
+    const uint16_t probe = 1;
+    if (*(const unsigned char*)&probe != 1) return fail("--colours", RT_E_UNSUPPORTED, "little-endian hosts only");
+    const size_t n = rays.size() / 6;
+    std::vector<float> rgb(n * 3);
+    const int rc = n == 0 ? 0
+                   : cpu  ? rt_cpu_shade_rays(c, &frame, rays.data(), (int64_t)n, rgb.data())
+                          : rt_shade_rays(c, &frame, rays.data(), (int64_t)n, rgb.data());
+    if (rc) return fail("rt_shade_rays", rc, rt_last_error(c));
+    rt_stats st;
+    rt_last_stats(c, &st);
+    if (n) std::printf("[ETAT]: %zu rayons, %s, %.3f ms\n", n, st.kernel, st.kernel_ms);
+    if (write_npy(path, "<f4", (int)n, 3, 1, rgb.data(), n * 12)) return fail("fopen", -1, path);
     return 0;
 }
 
@@ -496,6 +519,7 @@ int main(int argc, char** argv)
     const char* rays_in = nullptr;
     const char* hits = nullptr;
     bool ray_bvh = false;
+    const char* colours = nullptr;
     const char* segs_in = nullptr;
     const char* filters = nullptr;
     for (int i = 2; i < argc; ++i) {
@@ -530,6 +554,11 @@ int main(int argc, char** argv)
         if (std::strcmp(argv[i], "--hits") == 0) {
             if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--hits needs a file prefix");
             hits = argv[++i];
+            continue;
+        }
+        if (std::strcmp(argv[i], "--colours") == 0) {
+            if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--colours needs a .npy file to write");
+            colours = argv[++i];
             continue;
         }
         if (std::strcmp(argv[i], "--segments") == 0) {
@@ -594,8 +623,8 @@ int main(int argc, char** argv)
     if (aov && (gpus != 1 || bands || gather == 1))
         return fail("arguments", RT_E_ARG,
                     "--aov renders on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
-    if ((rays_in != nullptr) != (hits != nullptr))
-        return fail("arguments", RT_E_ARG, "--rays IN.npy and --hits PREFIX go together");
+    if ((rays_in != nullptr) != (hits != nullptr || colours != nullptr))
+        return fail("arguments", RT_E_ARG, "--rays IN.npy goes with --hits PREFIX, --colours OUT.npy or both");
     if (rays_in && (gpus != 1 || bands || gather == 1))
         return fail("arguments", RT_E_ARG,
                     "--rays traces on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
@@ -647,7 +676,8 @@ int main(int argc, char** argv)
         if ((rc = rt_upload_scene(c, &flat))) return fail("rt_upload_scene", rc, rt_last_error(c));
         if (rays_in) {
             std::printf("[ETAT]: Lancer de rayons (%zu rayons de %s)...\n", rays.size() / 6, rays_in);
-            if (write_hits(c, cpu, rays, hits)) return 1;
+            if (hits && write_hits(c, cpu, rays, hits)) return 1;
+            if (colours && write_colours(c, cpu, frame, rays, colours)) return 1;
         }
         if (segs_in) {
             std::printf("[ETAT]: Filtres d'ombre (%zu segments de %s)...\n", segs.size() / 6, segs_in);

@@ -38,7 +38,8 @@ constexpr int kCullClustered = 2;  // wave-level, two-level: the "big list" kern
 constexpr int kLightBuf = 4;  // shadow rays through the light buffer, one light per pass (rt_lightbuf.h)
 constexpr int kCamBuf = 8;    // camera rays walk the camera buffer's tile lists (rt_cambuf.h); a no-op in a
                               // launch whose S.cb_tiles_x is 0
-// (16 is unused)
+constexpr int kRayQuery = 16;  // the first ray is the caller's, not a camera ray: it is searched like a bounce ray
+                               // (rt_shaderays.h; closest_hit<false> or, with kBvh, closest_hit_bvh)
 constexpr int kTiny = 32;          // the camera records come with the launch (tiny scenes, rt_trace_tiny;
                                    // rt_cull.h TinyLaunch)
 constexpr int kMaskCompute = 64;   // ... and the wave computes its tile's mask instead of reading it
@@ -54,6 +55,7 @@ constexpr bool culls_by_wave(int w) { return cull_mode(w) != kCullNone; }
 constexpr bool is_clustered(int w) { return cull_mode(w) == kCullClustered; }
 constexpr bool has_light_buf(int w) { return (w & kLightBuf) != 0; }
 constexpr bool has_cam_buf(int w) { return (w & kCamBuf) != 0; }
+constexpr bool is_ray_query(int w) { return (w & kRayQuery) != 0; }
 constexpr bool is_tiny(int w) { return (w & kTiny) != 0; }
 constexpr bool computes_mask(int w) { return (w & kMaskCompute) != 0; }
 constexpr bool stores_mask(int w) { return (w & kMaskStore) != 0; }
@@ -93,6 +95,8 @@ static_assert((kBigList | kLbPair | kWf0) == 2566 && (kBigList | kCamBuf | kLbPa
 static_assert(kTinyRead == 37 && kTinyCompute == 101 && kTinyStore == 229, "");
 static_assert(kBvhSmall == 269 && kBvhBig == 270 && (kBvhSmall | kChain) == 1293 && (kBvhBig | kChain) == 1294, "");
 static_assert((kCullWave | kCamBuf) == 9 && (kCullClustered | kCamBuf) == 10, "");
+static_assert(kRayQuery == 16 && (kRayQuery | kSmallList) == 21 && (kRayQuery | kBigList) == 22, "");
+static_assert((kRayQuery | kBvh | kSmallList) == 277 && (kRayQuery | kBvh | kBigList) == 278, "");
 
 // ---- the instantiated variants: (MAXD, LB, flags) of every kernel the
 // build compiles, one list per kernel template, each entry through RT_V.
@@ -131,6 +135,19 @@ static_assert((kCullWave | kCamBuf) == 9 && (kCullClustered | kCamBuf) == 10, ""
 #define RT_AOV_VARIANTS                                                                       \
     RT_V(0, 1, kCullWave) RT_V(0, 1, kCullWave | kCamBuf) RT_V(0, 1, kCullClustered)          \
     RT_V(0, 1, kCullClustered | kCamBuf) RT_V(0, 1, kCullNone)
+// rt_shade_rays_kernel<MAXD, LB, flags> (rt_shaderays.h), radiance queries of
+// the caller's own rays.  A thinner depth list than the frames' bounds the
+// build time; the host takes the smallest entry that covers the reachable
+// depth (select_query_variant).  Plain: every surface per ray, per-lane
+// shadows.  Lit (depth 0 only): triangles with the light buffer.  BVH (every
+// depth): the first ray walks the tree like the others.  No kChain (the DFS
+// gives the same bits), no kLbPair, no kCamBuf (there is no camera).
+#define RT_QUERY_DEPTHS(X) X(0) X(1) X(2) X(3) X(5) X(8) X(16) X(32)
+#define RT_SHADE_RAYS_AT(N) \
+    RT_V(N, 1, kRayQuery | kBvh | kBigList) RT_V(N, 1, kRayQuery | kBvh | kSmallList) RT_V(N, 1, kRayQuery)
+#define RT_SHADE_RAYS_VARIANTS                                             \
+    RT_V(0, 1, kRayQuery | kBigList) RT_V(0, 1, kRayQuery | kSmallList) \
+    RT_QUERY_DEPTHS(RT_SHADE_RAYS_AT)
 
 // ---- the selection
 struct Variant {
@@ -187,6 +204,29 @@ constexpr Variant select_variant(const Facts& f)
 #define RT_DEPTH(N) \
     if (f.depth <= N) return Variant{N, 1, flags};
     RT_STACK_DEPTHS(RT_DEPTH)
+#undef RT_DEPTH
+    return Variant{};
+}
+
+// What the choice of a radiance query's kernel depends on (rt.h
+// rt_shade_rays): no camera, no frame size.
+struct QueryFacts {
+    int depth = 0;      // deepest bounce level a ray can reach
+    int n_tri = 0;
+    bool lbuf = false;  // shadow rays through the light buffer
+    bool bvh = false;   // the scene has the tree and ray queries walk it (RT_OPT_BVH, RT_OPT_RAY_BVH)
+};
+constexpr Variant select_query_variant(const QueryFacts& f)
+{
+    int flags = kRayQuery;
+    if (f.lbuf && f.n_tri > 0) {
+        const int lit = f.n_tri > kClusterMinTriangles ? kBigList : kSmallList;
+        if (f.bvh) flags |= kBvh | lit;
+        else if (f.depth == 0) flags |= lit;
+    }
+#define RT_DEPTH(N) \
+    if (f.depth <= N) return Variant{N, 1, flags};
+    RT_QUERY_DEPTHS(RT_DEPTH)
 #undef RT_DEPTH
     return Variant{};
 }

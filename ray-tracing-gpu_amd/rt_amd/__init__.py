@@ -133,6 +133,9 @@ SIGNATURES = {
     "rt_filter_rays": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP]),
     "rt_filter_rays_async": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP, _VP]),
     "rt_cpu_filter_rays": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP]),
+    "rt_shade_rays": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP, ctypes.c_int64, _VP]),
+    "rt_shade_rays_async": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP, ctypes.c_int64, _VP, _VP]),
+    "rt_cpu_shade_rays": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP, ctypes.c_int64, _VP]),
     "rt_upload_scene": (ctypes.c_int, [_VP, ctypes.POINTER(SceneFlat)]),
     "rt_render": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
     "rt_render_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), _VP]),
@@ -213,6 +216,14 @@ def _segments(segs):
     if s.ndim != 2 or s.shape[1] != 6:
         raise ValueError("segs: an (N, 6) array [Px Py Pz Lx Ly Lz]")
     return s, np.zeros((s.shape[0], 3), np.float32)
+
+
+def _shade_rays(rays):
+    """The (N, 6) float32 ray array and the (N, 3) float32 array its colours go to."""
+    r = np.ascontiguousarray(rays, np.float32)
+    if r.ndim != 2 or r.shape[1] != 6:
+        raise ValueError("rays: an (N, 6) array [Ox Oy Oz Dx Dy Dz]")
+    return r, np.zeros((r.shape[0], 3), np.float32)
 
 
 def _option(name) -> int:
@@ -439,6 +450,23 @@ class Context:
         _check("rt_filter_rays_async", lib().rt_filter_rays_async(self._h, segs_dev_ptr or None, int(count),
                                                                   filter_dev_ptr or None, stream or None), self._err)
 
+    def shade_rays(self, rays, frame: Frame) -> np.ndarray:
+        """rt_shade_rays: the colour ObtenirCouleur returns for each ray of the
+        (N, 6) array [Ox Oy Oz Dx Dy Dz] (D as given, not normalised) -> (N, 3)
+        float32.  Of `frame`, max_bounces, min_energy, scene_ior and background
+        are read; its camera and resolution play no part."""
+        r, out = _shade_rays(rays)
+        _check("rt_shade_rays", lib().rt_shade_rays(self._h, ctypes.byref(frame), r.ctypes.data, r.shape[0],
+                                                    out.ctypes.data), self._err)
+        return out
+
+    def shade_rays_async(self, frame: Frame, rays_dev_ptr: int, count: int, rgb_dev_ptr: int, stream: int = 0):
+        """rt_shade_rays_async: device pointers to `count` rays and to their 3 x `count` floats, enqueued
+        on `stream`."""
+        _check("rt_shade_rays_async", lib().rt_shade_rays_async(self._h, ctypes.byref(frame), rays_dev_ptr or None,
+                                                                int(count), rgb_dev_ptr or None, stream or None),
+               self._err)
+
     def stats(self) -> Stats:
         s = Stats()
         _check("rt_last_stats", lib().rt_last_stats(self._h, ctypes.byref(s)))
@@ -536,6 +564,13 @@ class CpuContext:
         s, out = _segments(segs)
         _check("rt_cpu_filter_rays", lib().rt_cpu_filter_rays(self._h, s.ctypes.data, s.shape[0], out.ctypes.data),
                self._err)
+        return out
+
+    def shade_rays(self, rays, frame: Frame) -> np.ndarray:
+        """rt_cpu_shade_rays: as Context.shade_rays, on host threads."""
+        r, out = _shade_rays(rays)
+        _check("rt_cpu_shade_rays", lib().rt_cpu_shade_rays(self._h, ctypes.byref(frame), r.ctypes.data, r.shape[0],
+                                                            out.ctypes.data), self._err)
         return out
 
     def stats(self) -> Stats:
@@ -647,3 +682,12 @@ class CScene:
         Context.filter_rays returns them."""
         self._prepared()
         return self._ctx.filter_rays(segs)
+
+    def LancerListeDeRayonsCouleur(self, rays) -> np.ndarray:
+        """ObtenirCouleur for the caller's own rays (not a verb of the
+        reference): (N, 6) [Ox Oy Oz Dx Dy Dz] -> (N, 3) float32 as
+        Context.shade_rays returns them, with the bounce depth, energy
+        threshold and index of refraction set through the Ajuster verbs; the
+        resolution and the supersampling play no part."""
+        f = self._frame()
+        return self._ctx.shade_rays(rays, f)

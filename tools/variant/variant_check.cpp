@@ -10,8 +10,10 @@
 //     form is in the list of its kernel template, so the host never asks for
 //     a kernel the build did not instantiate; the lists hold no entry twice; and
 //     kernel_name spells what printf would.
-// (b) select_variant() and lds_bytes() against expected results written out
-//     below, one per branch of the selection.
+//     The same for select_query_variant() and RT_SHADE_RAYS_VARIANTS, the
+//     radiance queries' kernels.
+// (b) select_variant(), select_query_variant() and lds_bytes() against
+//     expected results written out below, one per branch of the selection.
 // Prints "variant_check: ok (N selections)", exit 0; else exit 1.
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +37,7 @@ static const Variant kFrameList[] = {RT_TRACE_FRAME_VARIANTS};
 static const Variant kTinyList[] = {RT_TINY_VARIANTS};
 static const Variant kWfShadeList[] = {RT_WF_SHADE_VARIANTS};
 static const Variant kAovList[] = {RT_AOV_VARIANTS};
+static const Variant kShadeRaysList[] = {RT_SHADE_RAYS_VARIANTS};
 #undef RT_V
 
 template <size_t N>
@@ -123,6 +126,41 @@ static void walk()
                                 const unsigned lds = lds_bytes(v.flags, f.bvh_depth);
                                 REQUIRE((lds >= kLdsWaveBytes) == (is_clustered(v.flags) || has_bvh(v.flags)));
                             }
+}
+
+// (a) for the radiance queries (select_query_variant): every depth, triangle
+// count, light buffer and tree the host can form.  A tree without triangles
+// is left out (scene_host_bvh builds none below 64).
+static void walk_queries()
+{
+    static const int tris[] = {0, 1, 63, 64, 1024, 1025, 50000};
+    for (int depth = 0; depth <= 33; ++depth)
+        for (int n_tri : tris)
+            for (int bits = 0; bits < 4; ++bits) {
+                QueryFacts q;
+                q.depth = depth;
+                q.n_tri = n_tri;
+                q.lbuf = (bits & 1) != 0;
+                q.bvh = (bits & 2) != 0;
+                if (q.bvh && n_tri < 64) continue;
+                const Variant v = select_query_variant(q);
+                ++g_selections;
+                if (depth > 32) {
+                    REQUIRE(v.maxd < 0);
+                    continue;
+                }
+                REQUIRE(v.maxd >= depth && v.lb == 1 && count_of(kShadeRaysList, v) == 1);
+                REQUIRE(is_ray_query(v.flags) && !has_cam_buf(v.flags) && !is_chain(v.flags) && !has_lb_pair(v.flags));
+                REQUIRE(!is_wf0(v.flags) && !is_tiny(v.flags));
+                // the smallest entry of the thinner depth list
+                for (const Variant& e : kShadeRaysList) REQUIRE(!(e.flags == v.flags && e.maxd >= depth && e.maxd < v.maxd));
+                // the tree only with the light buffer; the light buffer alone only without bounces
+                REQUIRE(has_bvh(v.flags) == (q.bvh && q.lbuf));
+                REQUIRE(has_light_buf(v.flags) == (q.lbuf && n_tri > 0 && (q.bvh || depth == 0)));
+                REQUIRE(is_clustered(v.flags) == (has_light_buf(v.flags) && n_tri > 1024));
+                const unsigned lds = lds_bytes(v.flags, 24);
+                REQUIRE((lds >= kLdsWaveBytes) == (is_clustered(v.flags) || has_bvh(v.flags)));
+            }
 }
 
 // (b) expected results, written out (not computed by the code under test)
@@ -262,6 +300,32 @@ static void literals()
         f.cbuf = false;
         EXPECT(f, 0, 1, 2, win);
     }
+    // radiance queries: <stack, 1, flags>
+    {
+        auto query = [](int depth, int n_tri, bool lbuf, bool bvh) {
+            QueryFacts q;
+            q.depth = depth;
+            q.n_tri = n_tri;
+            q.lbuf = lbuf;
+            q.bvh = bvh;
+            return select_query_variant(q);
+        };
+        REQUIRE((query(0, 0, true, false) == Variant{0, 1, 16}));
+        REQUIRE((query(0, 12, true, false) == Variant{0, 1, 21}));
+        REQUIRE((query(0, 1025, true, false) == Variant{0, 1, 22}));
+        REQUIRE((query(0, 12, false, false) == Variant{0, 1, 16}));
+        REQUIRE((query(0, 1024, true, true) == Variant{0, 1, 277}));
+        REQUIRE((query(0, 1025, true, true) == Variant{0, 1, 278}));
+        REQUIRE((query(3, 1025, true, true) == Variant{3, 1, 278}));
+        REQUIRE((query(3, 1025, false, true) == Variant{3, 1, 16}));  // no light buffer: no BVH instance
+        REQUIRE((query(3, 1025, true, false) == Variant{3, 1, 16}));
+        REQUIRE((query(4, 64, true, true) == Variant{5, 1, 277}));    // the thinner depth list
+        REQUIRE((query(6, 0, false, false) == Variant{8, 1, 16}));
+        REQUIRE((query(9, 0, false, false) == Variant{16, 1, 16}));
+        REQUIRE((query(17, 0, false, false) == Variant{32, 1, 16}));
+        REQUIRE(query(33, 0, false, false).maxd == -1);
+        g_selections += 14;
+    }
     // the frame threshold
     REQUIRE(small_frame(3999999.0) && !small_frame(4000000.0));
 }
@@ -273,8 +337,12 @@ int main()
     check_list(kTinyList, "rt_trace_tiny", 3);
     check_list(kWfShadeList, "rt_wf_shade", 1);
     check_list(kAovList, "rt_aov_kernel", 1);
+    check_list(kShadeRaysList, "rt_shade_rays_kernel", 3);
+    for (const Variant& v : kShadeRaysList) REQUIRE(is_ray_query(v.flags) && count_of(kFrameList, v) == 0);
+    for (const Variant& v : kFrameList) REQUIRE(!is_ray_query(v.flags));
     for (const Variant& v : kWf0List) REQUIRE(count_of(kFrameList, v) == 0 && is_wf0(v.flags));
     walk();
+    walk_queries();
     literals();
     std::printf("variant_check: ok (%d selections)\n", g_selections);
     return 0;
