@@ -346,57 +346,77 @@ static int out_row(const rt_frame& f, int q)
     return (b * f.band_count + f.band_index) * f.band_rows + q % f.band_rows;
 }
 
+// The work pool of every entry point below: [0, n) in chunks of `chunk` items
+// handed from an atomic counter to `threads` host threads (0: one per hardware
+// thread; never more than there are chunks), the caller among them, and
+// body(begin, end) per chunk.  *ms: the wall time of the whole.
+template <class Body>
+static void for_chunks(int threads, int64_t n, int64_t chunk, double* ms, const Body& body)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    std::atomic<int64_t> next{0};
+    auto work = [&]() {
+        for (int64_t i0; (i0 = next.fetch_add(chunk)) < n;) body(i0, std::min(n, i0 + chunk));
+    };
+    int64_t k = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());
+    k = std::max<int64_t>(1, std::min(k, (n + chunk - 1) / chunk));
+    std::vector<std::thread> pool;
+    for (int64_t i = 1; i < k; ++i) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+constexpr int64_t kRowChunk = 8, kRayChunk = 256;  // rows of a frame, items of a query
+
+static void store3(float* out, size_t i, float a, float b, float c)
+{
+    out[3 * i] = a;
+    out[3 * i + 1] = b;
+    out[3 * i + 2] = c;
+}
+
+// One closest-hit result (the AOV pass's and rt_trace_rays's): a miss is the
+// reference's empty CIntersection.
+static void store_hit(const cpu::Scene& S, Vec3 O, Vec3 D, size_t o, float* out_t, int32_t* out_id, float* out_n)
+{
+    using namespace cpu;
+    const Hit h = closest(S, O, D);
+    if (out_t) out_t[o] = h.file < 0 ? -1.0f : h.t;
+    if (out_id) out_id[o] = h.file;
+    if (out_n) {
+        const Vec3 N = h.file < 0 ? make3(0.0f, 0.0f, 0.0f) : normal_of(S, h.file, O, D, h.t);
+        store3(out_n, o, N.x, N.y, N.z);
+    }
+}
+
 int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uint8_t* rgba, float* rgb, double* ms,
                unsigned long long* rays2)
 {
     using namespace cpu;
     const Scene& S = *static_cast<const Scene*>(handle);
-    const auto t0 = std::chrono::steady_clock::now();
     const int W = f->width;
-    std::atomic<int> next{0};
+    const Vec3 O = make3(f->cam_pos[0], f->cam_pos[1], f->cam_pos[2]);
     std::atomic<unsigned long long> primary{0}, bounce{0};
-    constexpr int kBand = 8;
-    auto work = [&]() {
+    for_chunks(threads, rows, kRowChunk, ms, [&](int64_t q0, int64_t q1) {
         tl_rays[0] = tl_rays[1] = 0;
-        for (;;) {
-            const int q0 = next.fetch_add(kBand);
-            if (q0 >= rows) {
-                primary += tl_rays[0];
-                bounce += tl_rays[1];
-                return;
-            }
-            for (int q = q0; q < std::min(rows, q0 + kBand); ++q) {
-                const int y = out_row(*f, q);
-                for (int x = 0; x < W; ++x) {
-                    const size_t o = (size_t)q * W + x;
-                    if (y >= f->height) {  // a band row past the frame: left unwritten, like the kernel
-                        continue;
-                    }
-                    const Ray r{make3(f->cam_pos[0], f->cam_pos[1], f->cam_pos[2]), camera_dir(*f, x, y), 1.0f,
-                                1.0f, 0};
-                    const Color c = trace(S, *f, r);
-                    if (rgb) {
-                        rgb[3 * o] = c.r;
-                        rgb[3 * o + 1] = c.g;
-                        rgb[3 * o + 2] = c.b;
-                    }
-                    if (rgba) {
-                        rgba[4 * o] = (uint8_t)unorm8(c.r);
-                        rgba[4 * o + 1] = (uint8_t)unorm8(c.g);
-                        rgba[4 * o + 2] = (uint8_t)unorm8(c.b);
-                        rgba[4 * o + 3] = 255;
-                    }
+        for (int q = (int)q0; q < (int)q1; ++q) {
+            const int y = out_row(*f, q);
+            if (y >= f->height) continue;  // a band row past the frame: left unwritten, like the kernel
+            for (int x = 0; x < W; ++x) {
+                const size_t o = (size_t)q * W + x;
+                const Color c = trace(S, *f, Ray{O, camera_dir(*f, x, y), 1.0f, 1.0f, 0});
+                if (rgb) store3(rgb, o, c.r, c.g, c.b);
+                if (rgba) {
+                    rgba[4 * o] = (uint8_t)unorm8(c.r);
+                    rgba[4 * o + 1] = (uint8_t)unorm8(c.g);
+                    rgba[4 * o + 2] = (uint8_t)unorm8(c.b);
+                    rgba[4 * o + 3] = 255;
                 }
             }
         }
-    };
-    int n = threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    n = std::max(1, std::min(n, (rows + kBand - 1) / kBand));
-    std::vector<std::thread> pool;
-    for (int i = 1; i < n; ++i) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        primary += tl_rays[0];
+        bounce += tl_rays[1];
+    });
     if (rays2) {
         rays2[0] = primary;
         rays2[1] = bounce;
@@ -406,155 +426,72 @@ int cpu_render(const void* handle, int threads, const rt_frame* f, int rows, uin
 
 // The AOV pass (rt.h rt_render_aov): the primary hit of every pixel, the
 // kernel's values bit for bit (the same closest / normal_of the colour path
-// uses).  A miss is the reference's empty CIntersection.
+// uses).
 int cpu_render_aov(const void* handle, int threads, const rt_frame* f, int rows, float* out_t, int32_t* out_id,
                    float* out_n, double* ms)
 {
     using namespace cpu;
     const Scene& S = *static_cast<const Scene*>(handle);
-    const auto t0 = std::chrono::steady_clock::now();
     const int W = f->width;
     const Vec3 O = make3(f->cam_pos[0], f->cam_pos[1], f->cam_pos[2]);
-    std::atomic<int> next{0};
-    constexpr int kBand = 8;
-    auto work = [&]() {
-        for (;;) {
-            const int q0 = next.fetch_add(kBand);
-            if (q0 >= rows) return;
-            for (int q = q0; q < std::min(rows, q0 + kBand); ++q) {
-                const int y = out_row(*f, q);
-                if (y >= f->height) continue;  // a band row past the frame: left unwritten, like the kernel
-                for (int x = 0; x < W; ++x) {
-                    const size_t o = (size_t)q * W + x;
-                    const Vec3 D = camera_dir(*f, x, y);
-                    const Hit h = closest(S, O, D);
-                    if (out_t) out_t[o] = h.file < 0 ? -1.0f : h.t;
-                    if (out_id) out_id[o] = h.file;
-                    if (out_n) {
-                        const Vec3 N = h.file < 0 ? make3(0.0f, 0.0f, 0.0f) : normal_of(S, h.file, O, D, h.t);
-                        out_n[3 * o] = N.x;
-                        out_n[3 * o + 1] = N.y;
-                        out_n[3 * o + 2] = N.z;
-                    }
-                }
-            }
+    for_chunks(threads, rows, kRowChunk, ms, [&](int64_t q0, int64_t q1) {
+        for (int q = (int)q0; q < (int)q1; ++q) {
+            const int y = out_row(*f, q);
+            if (y >= f->height) continue;  // a band row past the frame: left unwritten, like the kernel
+            for (int x = 0; x < W; ++x) store_hit(S, O, camera_dir(*f, x, y), (size_t)q * W + x, out_t, out_id, out_n);
         }
-    };
-    int n = threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    n = std::max(1, std::min(n, (rows + kBand - 1) / kBand));
-    std::vector<std::thread> pool;
-    for (int i = 1; i < n; ++i) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    });
     return RT_OK;
 }
 
-// Ray queries (rt.h rt_trace_rays): closest and normal_of per ray, chunks of
-// kChunk rays handed to the host threads from an atomic counter.
+// Ray queries (rt.h rt_trace_rays): closest and normal_of per ray.
 int cpu_trace_rays(const void* handle, int threads, const float* rays, int64_t n, float* out_t, int32_t* out_id,
                    float* out_n, double* ms)
 {
     using namespace cpu;
     const Scene& S = *static_cast<const Scene*>(handle);
-    const auto t0 = std::chrono::steady_clock::now();
-    std::atomic<int64_t> next{0};
-    constexpr int64_t kChunk = 256;
-    auto work = [&]() {
-        for (;;) {
-            const int64_t i0 = next.fetch_add(kChunk);
-            if (i0 >= n) return;
-            for (int64_t i = i0; i < std::min(n, i0 + kChunk); ++i) {
-                const float* r = rays + 6 * (size_t)i;
-                const Vec3 O = make3(r[0], r[1], r[2]), D = make3(r[3], r[4], r[5]);
-                const Hit h = closest(S, O, D);
-                if (out_t) out_t[i] = h.file < 0 ? -1.0f : h.t;
-                if (out_id) out_id[i] = h.file;
-                if (out_n) {
-                    const Vec3 N = h.file < 0 ? make3(0.0f, 0.0f, 0.0f) : normal_of(S, h.file, O, D, h.t);
-                    out_n[3 * i] = N.x;
-                    out_n[3 * i + 1] = N.y;
-                    out_n[3 * i + 2] = N.z;
-                }
-            }
+    for_chunks(threads, n, kRayChunk, ms, [&](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const float* r = rays + 6 * (size_t)i;
+            store_hit(S, make3(r[0], r[1], r[2]), make3(r[3], r[4], r[5]), (size_t)i, out_t, out_id, out_n);
         }
-    };
-    int64_t k = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());
-    k = std::max<int64_t>(1, std::min(k, (n + kChunk - 1) / kChunk));
-    std::vector<std::thread> pool;
-    for (int64_t i = 1; i < k; ++i) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    });
     return RT_OK;
 }
 
 // Filter queries (rt.h rt_filter_rays): the shadow rays' own filter() per
-// segment, chunked like cpu_trace_rays.
+// segment.
 int cpu_filter_rays(const void* handle, int threads, const float* segs, int64_t n, float* out, double* ms)
 {
     using namespace cpu;
     const Scene& S = *static_cast<const Scene*>(handle);
-    const auto t0 = std::chrono::steady_clock::now();
-    std::atomic<int64_t> next{0};
-    constexpr int64_t kChunk = 256;
-    auto work = [&]() {
-        for (;;) {
-            const int64_t i0 = next.fetch_add(kChunk);
-            if (i0 >= n) return;
-            for (int64_t i = i0; i < std::min(n, i0 + kChunk); ++i) {
-                const float* r = segs + 6 * (size_t)i;
-                Vec3 L = make3(r[3], r[4], r[5]);
-                const Color F = filter(S, make3(r[0], r[1], r[2]), L);
-                out[3 * i] = F.r;
-                out[3 * i + 1] = F.g;
-                out[3 * i + 2] = F.b;
-            }
+    for_chunks(threads, n, kRayChunk, ms, [&](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const float* r = segs + 6 * (size_t)i;
+            Vec3 L = make3(r[3], r[4], r[5]);
+            const Color F = filter(S, make3(r[0], r[1], r[2]), L);
+            store3(out, (size_t)i, F.r, F.g, F.b);
         }
-    };
-    int64_t k = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());
-    k = std::max<int64_t>(1, std::min(k, (n + kChunk - 1) / kChunk));
-    std::vector<std::thread> pool;
-    for (int64_t i = 1; i < k; ++i) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    });
     return RT_OK;
 }
 
 // Radiance queries (rt.h rt_shade_rays): the frames' own trace() per ray —
 // a camera ray's state (energy 1, 0 bounces, IOR 1) with the caller's O and
-// D as given —, chunked like cpu_trace_rays.  Of f, trace() reads
-// max_bounces, min_energy, scene_ior and background.
+// D as given.  Of f, trace() reads max_bounces, min_energy, scene_ior and
+// background.
 int cpu_shade_rays(const void* handle, int threads, const rt_frame* f, const float* rays, int64_t n, float* out,
                    double* ms)
 {
     using namespace cpu;
     const Scene& S = *static_cast<const Scene*>(handle);
-    const auto t0 = std::chrono::steady_clock::now();
-    std::atomic<int64_t> next{0};
-    constexpr int64_t kChunk = 256;
-    auto work = [&]() {
-        for (;;) {
-            const int64_t i0 = next.fetch_add(kChunk);
-            if (i0 >= n) return;
-            for (int64_t i = i0; i < std::min(n, i0 + kChunk); ++i) {
-                const float* r = rays + 6 * (size_t)i;
-                const Ray ray{make3(r[0], r[1], r[2]), make3(r[3], r[4], r[5]), 1.0f, 1.0f, 0};
-                const Color c = trace(S, *f, ray);
-                out[3 * i] = c.r;
-                out[3 * i + 1] = c.g;
-                out[3 * i + 2] = c.b;
-            }
+    for_chunks(threads, n, kRayChunk, ms, [&](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const float* r = rays + 6 * (size_t)i;
+            const Color c = trace(S, *f, Ray{make3(r[0], r[1], r[2]), make3(r[3], r[4], r[5]), 1.0f, 1.0f, 0});
+            store3(out, (size_t)i, c.r, c.g, c.b);
         }
-    };
-    int64_t k = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());
-    k = std::max<int64_t>(1, std::min(k, (n + kChunk - 1) / kChunk));
-    std::vector<std::thread> pool;
-    for (int64_t i = 1; i < k; ++i) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    });
     return RT_OK;
 }
 

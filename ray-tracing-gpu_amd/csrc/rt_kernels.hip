@@ -3659,35 +3659,155 @@ RT_EXPORT int rt_cpu_render_aov(rt_ctx* c, const rt_frame* f, const rt_aov* out)
     return rc;
 }
 
-// ---- closest-hit queries of arbitrary rays (rt.h rt_trace_rays*, rt_rays.h)
-// The checks every ray entry point shares (after the backend's own).  *go:
-// there is something to trace (n == 0 is RT_OK with nothing written).
-static int rays_check(rt_ctx* c, const float* rays, int64_t n, const rt_aov* o, bool* go)
+// ---- queries of arbitrary rays: closest hits (rt.h rt_trace_rays*, rt_rays.h),
+// shadow filters of segments (rt_filter_rays*, rt_filter.h) and radiance
+// (rt_shade_rays*, rt_shaderays.h).  One host path (query_check, query_sync,
+// query_async, query_cpu); a QueryKind says what differs between the three,
+// a Query is one call.
+struct Query;
+struct QueryKind {
+    const char* name;   // the synchronous entry point rt_<stem>: rt_<stem>_async, rt_cpu_<stem>, cpu_<stem>
+    const char* noun;   // "the <noun> count must be ..."
+    const char* nulls;  // the message for a null input or output
+    int out_bytes[3];   // bytes per item of each output plane (0: the query has no such plane)
+    bool optional_out;  // a null plane is not requested (one at least) / every plane is required
+    bool takes_frame;   // the call carries an rt_frame of parameters
+    uint64_t rt_stats::*count;                // the counter of c->last that takes n
+    int (*pick)(rt_ctx*, Query&);             // the kernel for the call's parameters (null: nothing to pick)
+    void (*label)(rt_ctx*, const Query&);     // c->last's kernel name, and what goes with it
+    int (*launch)(rt_ctx*, const Query&, const float* d_in, void* const d_out[3], hipStream_t);
+    int (*cpu)(rt_ctx*, const Query&, double* ms);
+};
+struct Query {
+    const QueryKind& k;
+    const rt_frame* f;  // (takes_frame)
+    const float* in;    // n x 6 floats
+    int64_t n;
+    void* out[3];
+    KernelPick kp;      // (pick)
+};
+
+// The checks every entry point shares, in the order rt.h documents.  *go:
+// there is something to do (n == 0 is RT_OK with nothing written).
+static int query_check(rt_ctx* c, Query& q, bool cpu, bool* go)
 {
+    const QueryKind& k = q.k;
     *go = false;
-    if (int rc = check_uploaded(c, "rt_trace_rays")) return rc;
-    if (n < 0 || n > INT32_MAX) {
-        c->err = "rt_trace_rays: the ray count must be 0 .. INT32_MAX";
+    if (!c) return RT_E_ARG;
+    if (c->cpu != cpu) return cpu ? needs_cpu(c, (std::string("rt_cpu_") + (k.name + 3)).c_str()) : not_cpu(c);
+    if (int rc = check_uploaded(c, k.name)) return rc;
+    if (k.takes_frame && !q.f) {
+        c->err = std::string(k.name) + ": no rt_frame (max_bounces, min_energy, scene_ior, background)";
         return RT_E_ARG;
     }
-    if (n == 0) return RT_OK;
-    if (!rays || !o || (!o->t && !o->id && !o->n)) {
-        c->err = "rt_trace_rays: no rays or no output plane";
+    if (q.n < 0 || q.n > INT32_MAX) {
+        c->err = std::string(k.name) + ": the " + k.noun + " count must be 0 .. INT32_MAX";
         return RT_E_ARG;
     }
+    if (q.n == 0) return RT_OK;
+    bool any = false, all = true;
+    for (int i = 0; i < 3; ++i) {
+        if (!k.out_bytes[i]) continue;
+        any = any || q.out[i];
+        all = all && q.out[i];
+    }
+    if (!q.in || !(k.optional_out ? any : all)) {
+        c->err = std::string(k.name) + ": " + k.nulls;
+        return RT_E_ARG;
+    }
+    // (a depth above the compiled stacks is refused before any pointer is classified)
+    if (!cpu && k.pick)
+        if (int rc = k.pick(c, q)) return rc;
     *go = true;
     return RT_OK;
 }
 
-static int rays_aligned(rt_ctx* c, const void* p)
+static int query_aligned(rt_ctx* c, const Query& q, const void* p)
 {
     if (((uintptr_t)p & 7u) == 0) return RT_OK;
-    c->err = "rt_trace_rays: device pointers must be 8-byte aligned";
+    c->err = std::string(q.k.name) + ": device pointers must be 8-byte aligned";
     return RT_E_ARG;
 }
 
-// The query walks the BVH whenever the scene has one (RT_OPT_BVH): the tree
-// of a scene that can bounce, or RT_OPT_RAY_BVH's.
+// Host or device pointers, on c->stream, timed.  The scratch: a host input
+// first, then one 256-byte aligned part per host output plane.
+static int query_sync(rt_ctx* c, Query q)
+{
+    const QueryKind& k = q.k;
+    bool go;
+    if (int rc = query_check(c, q, false, &go)) return rc;
+    if (!go) return RT_OK;
+    if (int rc = sync_begin(c)) return rc;
+    const bool in_host = !is_device_ptr(q.in);
+    const size_t n = (size_t)q.n, in_bytes = n * 6 * sizeof(float);
+    SyncOut o;
+    if (in_host) o.need = (in_bytes + 255) / 256 * 256;
+    for (int i = 0; i < 3; ++i) o.add(q.out[i], (n * k.out_bytes[i] + 255) / 256 * 256);
+    if (!in_host)
+        if (int rc = query_aligned(c, q, q.in)) return rc;
+    for (int i = 0; i < 3; ++i)
+        if (q.out[i] && !o.host[i])
+            if (int rc = query_aligned(c, q, q.out[i])) return rc;
+    if (int rc = o.place(c)) return rc;
+    const float* d_in = q.in;
+    if (in_host) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_scratch, q.in, in_bytes, hipMemcpyHostToDevice, c->stream));
+        d_in = (const float*)c->d_scratch;
+    }
+    c->last = rt_stats{};
+    k.label(c, q);
+    c->last.*k.count = (uint64_t)q.n;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    if (int rc = k.launch(c, q, d_in, o.target, c->stream)) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    for (int i = 0; i < 3; ++i)
+        if (int rc = o.copy_back(c, i, n * k.out_bytes[i])) return rc;
+    static const rt_frame no_frame{};  // (no RT_FLAG_STATS: a query has no counting instances)
+    return finish_sync(c, &no_frame, c->stream, true);
+}
+
+// Device pointers, enqueued on the caller's stream: one kernel and host
+// bookkeeping, no state of the context (legal inside a stream capture).
+static int query_async(rt_ctx* c, Query q, void* stream)
+{
+    bool go;
+    if (int rc = query_check(c, q, false, &go)) return rc;
+    if (!go) return RT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const void* const ptr[4] = {q.in, q.out[0], q.out[1], q.out[2]};
+    for (const void* p : ptr) {
+        if (!p) continue;
+        if (!is_device_ptr(p)) {
+            c->err = std::string(q.k.name) + "_async takes device pointers";
+            return RT_E_ARG;
+        }
+        if (int rc = query_aligned(c, q, p)) return rc;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    bool capturing = false;
+    if (int rc = stream_capturing(c, st, &capturing)) return rc;
+    if (int rc = q.k.launch(c, q, q.in, q.out, st)) return rc;
+    // (host bookkeeping only: an upload syncs st, or keeps what a graph references)
+    enqueued(c, st, capturing, nullptr);
+    return RT_OK;
+}
+
+static int query_cpu(rt_ctx* c, Query q)
+{
+    bool go;
+    if (int rc = query_check(c, q, true, &go)) return rc;
+    if (!go) return RT_OK;
+    c->last = rt_stats{};
+    double ms = 0.0;
+    const int rc = q.k.cpu(c, q, &ms);
+    c->last.kernel_ms = (float)ms;
+    c->last.*q.k.count = (uint64_t)q.n;
+    std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_%s", q.k.name + 3);
+    return rc;
+}
+
+// -- closest hits.  The query walks the BVH whenever the scene has one
+// (RT_OPT_BVH): the tree of a scene that can bounce, or RT_OPT_RAY_BVH's.
 static bool rays_bvh(const rt_ctx* c) { return c->d_bvh_node && c->opt_bvh; }
 
 // n rays into device planes on st: one kernel, no state of the context.
@@ -3706,115 +3826,43 @@ static int launch_rays(rt_ctx* c, const float* d_rays, int n, const rt_aov& dev,
     return RT_OK;
 }
 
+static const QueryKind kTraceRays = {
+    "rt_trace_rays", "ray", "no rays or no output plane", {4, 4, 12}, true, false, &rt_stats::bounce_rays, nullptr,
+    [](rt_ctx* c, const Query&) {
+        std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_rays_kernel<%d>", rays_bvh(c) ? 1 : 0);
+    },
+    [](rt_ctx* c, const Query& q, const float* d_in, void* const o[3], hipStream_t st) {
+        return launch_rays(c, d_in, (int)q.n, rt_aov{(float*)o[0], (int32_t*)o[1], (float*)o[2]}, st);
+    },
+    [](rt_ctx* c, const Query& q, double* ms) {
+        return cpu_trace_rays(c->cpu_scene, c->cpu_threads, q.in, q.n, (float*)q.out[0], (int32_t*)q.out[1],
+                              (float*)q.out[2], ms);
+    }};
+
+static Query trace_query(const float* rays, int64_t n, const rt_aov* o)
+{
+    const rt_aov none{};  // (no rt_aov at all: no plane requested)
+    if (!o) o = &none;
+    return Query{kTraceRays, nullptr, rays, n, {o->t, o->id, o->n}};
+}
+
 RT_EXPORT int rt_trace_rays(rt_ctx* c, const float* rays, int64_t n, const rt_aov* out)
 {
-    if (!c) return RT_E_ARG;
-    if (c->cpu) return not_cpu(c);
-    bool go;
-    if (int rc = rays_check(c, rays, n, out, &go)) return rc;
-    if (!go) return RT_OK;
-    if (int rc = sync_begin(c)) return rc;
-    // the scratch: a host ray array first, then one 256-byte aligned part per host plane
-    const bool rays_host = !is_device_ptr(rays);
-    const size_t rbytes = (size_t)n * 6 * sizeof(float);
-    void* const user[3] = {out->t, out->id, out->n};
-    SyncOut o;
-    if (rays_host) o.need = (rbytes + 255) / 256 * 256;
-    for (int i = 0; i < 3; ++i) o.add(user[i], ((size_t)n * (i == 2 ? 12 : 4) + 255) / 256 * 256);
-    if (!rays_host)
-        if (int rc = rays_aligned(c, rays)) return rc;
-    for (int i = 0; i < 3; ++i)
-        if (user[i] && !o.host[i])
-            if (int rc = rays_aligned(c, user[i])) return rc;
-    if (int rc = o.place(c)) return rc;
-    const float* d_rays = rays;
-    if (rays_host) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_scratch, rays, rbytes, hipMemcpyHostToDevice, c->stream));
-        d_rays = (const float*)c->d_scratch;
-    }
-    const rt_aov dev{(float*)o.target[0], (int32_t*)o.target[1], (float*)o.target[2]};
-    c->last = rt_stats{};
-    std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_rays_kernel<%d>", rays_bvh(c) ? 1 : 0);
-    c->last.bounce_rays = (uint64_t)n;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    if (int rc = launch_rays(c, d_rays, (int)n, dev, c->stream)) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    for (int i = 0; i < 3; ++i)
-        if (int rc = o.copy_back(c, i, (size_t)n * (i == 2 ? 12 : 4))) return rc;
-    static const rt_frame no_frame{};  // (no RT_FLAG_STATS)
-    return finish_sync(c, &no_frame, c->stream, true);
+    return query_sync(c, trace_query(rays, n, out));
 }
 
 RT_EXPORT int rt_trace_rays_async(rt_ctx* c, const float* dev_rays, int64_t n, const rt_aov* dev, void* stream)
 {
-    if (!c) return RT_E_ARG;
-    if (c->cpu) return not_cpu(c);
-    bool go;
-    if (int rc = rays_check(c, dev_rays, n, dev, &go)) return rc;
-    if (!go) return RT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const void* const ptr[4] = {dev_rays, dev->t, dev->id, dev->n};
-    for (const void* p : ptr) {
-        if (!p) continue;
-        if (!is_device_ptr(p)) {
-            c->err = "rt_trace_rays_async takes device pointers";
-            return RT_E_ARG;
-        }
-        if (int rc = rays_aligned(c, p)) return rc;
-    }
-    const hipStream_t st = (hipStream_t)stream;
-    bool capturing = false;
-    if (int rc = stream_capturing(c, st, &capturing)) return rc;
-    if (int rc = launch_rays(c, dev_rays, (int)n, *dev, st)) return rc;
-    // (host bookkeeping only: an upload syncs st, or keeps what a graph references)
-    enqueued(c, st, capturing, nullptr);
-    return RT_OK;
+    return query_async(c, trace_query(dev_rays, n, dev), stream);
 }
 
 RT_EXPORT int rt_cpu_trace_rays(rt_ctx* c, const float* rays, int64_t n, const rt_aov* out)
 {
-    if (!c) return RT_E_ARG;
-    if (!c->cpu) return needs_cpu(c, "rt_cpu_trace_rays");
-    bool go;
-    if (int rc = rays_check(c, rays, n, out, &go)) return rc;
-    if (!go) return RT_OK;
-    c->last = rt_stats{};
-    double ms = 0.0;
-    const int rc = cpu_trace_rays(c->cpu_scene, c->cpu_threads, rays, n, out->t, out->id, out->n, &ms);
-    c->last.kernel_ms = (float)ms;
-    c->last.bounce_rays = (uint64_t)n;
-    std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_trace_rays");
-    return rc;
+    return query_cpu(c, trace_query(rays, n, out));
 }
 
-// ---- shadow-filter queries of arbitrary segments (rt.h rt_filter_rays*, rt_filter.h)
-// The checks every filter entry point shares (rays_check's rules).
-static int filter_check(rt_ctx* c, const float* segs, int64_t n, const float* out, bool* go)
-{
-    *go = false;
-    if (int rc = check_uploaded(c, "rt_filter_rays")) return rc;
-    if (n < 0 || n > INT32_MAX) {
-        c->err = "rt_filter_rays: the segment count must be 0 .. INT32_MAX";
-        return RT_E_ARG;
-    }
-    if (n == 0) return RT_OK;
-    if (!segs || !out) {
-        c->err = "rt_filter_rays: no segments or no output";
-        return RT_E_ARG;
-    }
-    *go = true;
-    return RT_OK;
-}
-
-static int filter_aligned(rt_ctx* c, const void* p)
-{
-    if (((uintptr_t)p & 7u) == 0) return RT_OK;
-    c->err = "rt_filter_rays: device pointers must be 8-byte aligned";
-    return RT_E_ARG;
-}
-
-// The any-hit walk needs the tree and factors that are all finite and >= +0
-// (rt_filter.h); else the file-order product.
+// -- shadow filters.  The any-hit walk needs the tree and factors that are all
+// finite and >= +0 (rt_filter.h); else the file-order product.
 static bool filter_bvh_on(const rt_ctx* c) { return rays_bvh(c) && c->shadow_split; }
 
 // n segments into dev_out on st: one kernel, no state of the context.
@@ -3831,117 +3879,38 @@ static int launch_filter(rt_ctx* c, const float* d_segs, int n, float* d_out, hi
     return RT_OK;
 }
 
+static const QueryKind kFilterRays = {
+    "rt_filter_rays", "segment", "no segments or no output", {12, 0, 0}, false, false, &rt_stats::shadow_rays, nullptr,
+    [](rt_ctx* c, const Query&) {
+        std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_filter_kernel<%d>", filter_bvh_on(c) ? 1 : 0);
+    },
+    [](rt_ctx* c, const Query& q, const float* d_in, void* const o[3], hipStream_t st) {
+        return launch_filter(c, d_in, (int)q.n, (float*)o[0], st);
+    },
+    [](rt_ctx* c, const Query& q, double* ms) {
+        return cpu_filter_rays(c->cpu_scene, c->cpu_threads, q.in, q.n, (float*)q.out[0], ms);
+    }};
+
 RT_EXPORT int rt_filter_rays(rt_ctx* c, const float* segs, int64_t n, float* filter)
 {
-    if (!c) return RT_E_ARG;
-    if (c->cpu) return not_cpu(c);
-    bool go;
-    if (int rc = filter_check(c, segs, n, filter, &go)) return rc;
-    if (!go) return RT_OK;
-    if (int rc = sync_begin(c)) return rc;
-    // the scratch: a host segment array first, then the host output
-    const bool segs_host = !is_device_ptr(segs);
-    const size_t sbytes = (size_t)n * 6 * sizeof(float), obytes = (size_t)n * 3 * sizeof(float);
-    SyncOut o;
-    if (segs_host) o.need = (sbytes + 255) / 256 * 256;
-    o.add(filter, (obytes + 255) / 256 * 256);
-    if (!segs_host)
-        if (int rc = filter_aligned(c, segs)) return rc;
-    if (!o.host[0])
-        if (int rc = filter_aligned(c, filter)) return rc;
-    if (int rc = o.place(c)) return rc;
-    const float* d_segs = segs;
-    if (segs_host) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_scratch, segs, sbytes, hipMemcpyHostToDevice, c->stream));
-        d_segs = (const float*)c->d_scratch;
-    }
-    c->last = rt_stats{};
-    std::snprintf(c->last.kernel, sizeof c->last.kernel, "rt_filter_kernel<%d>", filter_bvh_on(c) ? 1 : 0);
-    c->last.shadow_rays = (uint64_t)n;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    if (int rc = launch_filter(c, d_segs, (int)n, (float*)o.target[0], c->stream)) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    if (int rc = o.copy_back(c, 0, obytes)) return rc;
-    static const rt_frame no_frame{};  // (no RT_FLAG_STATS)
-    return finish_sync(c, &no_frame, c->stream, true);
+    return query_sync(c, Query{kFilterRays, nullptr, segs, n, {filter}});
 }
 
 RT_EXPORT int rt_filter_rays_async(rt_ctx* c, const float* dev_segs, int64_t n, float* dev_filter, void* stream)
 {
-    if (!c) return RT_E_ARG;
-    if (c->cpu) return not_cpu(c);
-    bool go;
-    if (int rc = filter_check(c, dev_segs, n, dev_filter, &go)) return rc;
-    if (!go) return RT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const void* const ptr[2] = {dev_segs, dev_filter};
-    for (const void* p : ptr) {
-        if (!is_device_ptr(p)) {
-            c->err = "rt_filter_rays_async takes device pointers";
-            return RT_E_ARG;
-        }
-        if (int rc = filter_aligned(c, p)) return rc;
-    }
-    const hipStream_t st = (hipStream_t)stream;
-    bool capturing = false;
-    if (int rc = stream_capturing(c, st, &capturing)) return rc;
-    if (int rc = launch_filter(c, dev_segs, (int)n, dev_filter, st)) return rc;
-    // (host bookkeeping only: an upload syncs st, or keeps what a graph references)
-    enqueued(c, st, capturing, nullptr);
-    return RT_OK;
+    return query_async(c, Query{kFilterRays, nullptr, dev_segs, n, {dev_filter}}, stream);
 }
 
 RT_EXPORT int rt_cpu_filter_rays(rt_ctx* c, const float* segs, int64_t n, float* filter)
 {
-    if (!c) return RT_E_ARG;
-    if (!c->cpu) return needs_cpu(c, "rt_cpu_filter_rays");
-    bool go;
-    if (int rc = filter_check(c, segs, n, filter, &go)) return rc;
-    if (!go) return RT_OK;
-    c->last = rt_stats{};
-    double ms = 0.0;
-    const int rc = cpu_filter_rays(c->cpu_scene, c->cpu_threads, segs, n, filter, &ms);
-    c->last.kernel_ms = (float)ms;
-    c->last.shadow_rays = (uint64_t)n;
-    std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_filter_rays");
-    return rc;
+    return query_cpu(c, Query{kFilterRays, nullptr, segs, n, {filter}});
 }
 
-// ---- radiance queries of arbitrary rays (rt.h rt_shade_rays*, rt_shaderays.h)
+// -- radiance
 #define RT_V(M, L, F) \
     {{M, L, F}, {(const void*)&rt_shade_rays_kernel<M, L, F>}, kernel_name("rt_shade_rays_kernel", M, L, F)},
 static const KernelRow<1> kShadeRaysKernels[] = {RT_SHADE_RAYS_VARIANTS};
 #undef RT_V
-
-// The checks every shade entry point shares (filter_check's rules, and the
-// frame that carries the parameters).
-static int shade_rays_check(rt_ctx* c, const rt_frame* f, const float* rays, int64_t n, const float* out, bool* go)
-{
-    *go = false;
-    if (int rc = check_uploaded(c, "rt_shade_rays")) return rc;
-    if (!f) {
-        c->err = "rt_shade_rays: no rt_frame (max_bounces, min_energy, scene_ior, background)";
-        return RT_E_ARG;
-    }
-    if (n < 0 || n > INT32_MAX) {
-        c->err = "rt_shade_rays: the ray count must be 0 .. INT32_MAX";
-        return RT_E_ARG;
-    }
-    if (n == 0) return RT_OK;
-    if (!rays || !out) {
-        c->err = "rt_shade_rays: no rays or no output";
-        return RT_E_ARG;
-    }
-    *go = true;
-    return RT_OK;
-}
-
-static int shade_rays_aligned(rt_ctx* c, const void* p)
-{
-    if (((uintptr_t)p & 7u) == 0) return RT_OK;
-    c->err = "rt_shade_rays: device pointers must be 8-byte aligned";
-    return RT_E_ARG;
-}
 
 // The query's kernel for the parameters of f: select_query_variant's row
 // (k == nullptr: the reachable depth exceeds the compiled stacks).
@@ -3983,87 +3952,36 @@ static int launch_shade_rays(rt_ctx* c, const KernelPick& kp, const rt_frame* f,
     return RT_OK;
 }
 
+// (RT_FLAG_STATS in f->flags is ignored)
+static const QueryKind kShadeRays = {
+    "rt_shade_rays", "ray", "no rays or no output", {12, 0, 0}, false, true, &rt_stats::primary_rays,
+    [](rt_ctx* c, Query& q) { return pick_shade_rays(c, q.f, q.kp); },
+    [](rt_ctx* c, const Query& q) {
+        std::memcpy(c->last.kernel, q.kp.name->s, sizeof q.kp.name->s);
+        c->last.stack_depth = q.kp.v.maxd;
+        c->last.light_batch = q.kp.v.lb;
+    },
+    [](rt_ctx* c, const Query& q, const float* d_in, void* const o[3], hipStream_t st) {
+        return launch_shade_rays(c, q.kp, q.f, d_in, (int)q.n, (float*)o[0], st);
+    },
+    [](rt_ctx* c, const Query& q, double* ms) {
+        return cpu_shade_rays(c->cpu_scene, c->cpu_threads, q.f, q.in, q.n, (float*)q.out[0], ms);
+    }};
+
 RT_EXPORT int rt_shade_rays(rt_ctx* c, const rt_frame* f, const float* rays, int64_t n, float* rgb)
 {
-    if (!c) return RT_E_ARG;
-    if (c->cpu) return not_cpu(c);
-    bool go;
-    if (int rc = shade_rays_check(c, f, rays, n, rgb, &go)) return rc;
-    if (!go) return RT_OK;
-    KernelPick kp;
-    if (int rc = pick_shade_rays(c, f, kp)) return rc;
-    if (int rc = sync_begin(c)) return rc;
-    // the scratch: a host ray array first, then the host output
-    const bool rays_host = !is_device_ptr(rays);
-    const size_t rbytes = (size_t)n * 6 * sizeof(float), obytes = (size_t)n * 3 * sizeof(float);
-    SyncOut o;
-    if (rays_host) o.need = (rbytes + 255) / 256 * 256;
-    o.add(rgb, (obytes + 255) / 256 * 256);
-    if (!rays_host)
-        if (int rc = shade_rays_aligned(c, rays)) return rc;
-    if (!o.host[0])
-        if (int rc = shade_rays_aligned(c, rgb)) return rc;
-    if (int rc = o.place(c)) return rc;
-    const float* d_rays = rays;
-    if (rays_host) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_scratch, rays, rbytes, hipMemcpyHostToDevice, c->stream));
-        d_rays = (const float*)c->d_scratch;
-    }
-    c->last = rt_stats{};
-    std::memcpy(c->last.kernel, kp.name->s, sizeof kp.name->s);
-    c->last.primary_rays = (uint64_t)n;
-    c->last.stack_depth = kp.v.maxd;
-    c->last.light_batch = kp.v.lb;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    if (int rc = launch_shade_rays(c, kp, f, d_rays, (int)n, (float*)o.target[0], c->stream)) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    if (int rc = o.copy_back(c, 0, obytes)) return rc;
-    static const rt_frame no_frame{};  // (RT_FLAG_STATS in f->flags is ignored: no counting instances)
-    return finish_sync(c, &no_frame, c->stream, true);
+    return query_sync(c, Query{kShadeRays, f, rays, n, {rgb}});
 }
 
 RT_EXPORT int rt_shade_rays_async(rt_ctx* c, const rt_frame* f, const float* dev_rays, int64_t n, float* dev_rgb,
                                   void* stream)
 {
-    if (!c) return RT_E_ARG;
-    if (c->cpu) return not_cpu(c);
-    bool go;
-    if (int rc = shade_rays_check(c, f, dev_rays, n, dev_rgb, &go)) return rc;
-    if (!go) return RT_OK;
-    KernelPick kp;
-    if (int rc = pick_shade_rays(c, f, kp)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const void* const ptr[2] = {dev_rays, dev_rgb};
-    for (const void* p : ptr) {
-        if (!is_device_ptr(p)) {
-            c->err = "rt_shade_rays_async takes device pointers";
-            return RT_E_ARG;
-        }
-        if (int rc = shade_rays_aligned(c, p)) return rc;
-    }
-    const hipStream_t st = (hipStream_t)stream;
-    bool capturing = false;
-    if (int rc = stream_capturing(c, st, &capturing)) return rc;
-    if (int rc = launch_shade_rays(c, kp, f, dev_rays, (int)n, dev_rgb, st)) return rc;
-    // (host bookkeeping only: an upload syncs st, or keeps what a graph references)
-    enqueued(c, st, capturing, nullptr);
-    return RT_OK;
+    return query_async(c, Query{kShadeRays, f, dev_rays, n, {dev_rgb}}, stream);
 }
 
 RT_EXPORT int rt_cpu_shade_rays(rt_ctx* c, const rt_frame* f, const float* rays, int64_t n, float* rgb)
 {
-    if (!c) return RT_E_ARG;
-    if (!c->cpu) return needs_cpu(c, "rt_cpu_shade_rays");
-    bool go;
-    if (int rc = shade_rays_check(c, f, rays, n, rgb, &go)) return rc;
-    if (!go) return RT_OK;
-    c->last = rt_stats{};
-    double ms = 0.0;
-    const int rc = cpu_shade_rays(c->cpu_scene, c->cpu_threads, f, rays, n, rgb, &ms);
-    c->last.kernel_ms = (float)ms;
-    c->last.primary_rays = (uint64_t)n;
-    std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_shade_rays");
-    return rc;
+    return query_cpu(c, Query{kShadeRays, f, rays, n, {rgb}});
 }
 
 // Diagnostic (include/rt_debug.h): the resolve kernel alone.

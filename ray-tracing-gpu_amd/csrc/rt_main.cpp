@@ -223,11 +223,27 @@ static bool read_rays_npy(const char* path, std::vector<float>& rays, std::strin
     return true;
 }
 
+// The head of every query verb: refuses a big-endian host (the .npy are written little-endian).
+static int little_endian(const char* verb)
+{
+    const uint16_t probe = 1;
+    return *(const unsigned char*)&probe == 1 ? 0 : fail(verb, RT_E_UNSUPPORTED, "little-endian hosts only");
+}
+
+// After the query `call` returned rc for n items: the error, or the [ETAT] line.
+static int query_done(rt_ctx* c, const char* call, int rc, size_t n, const char* noun)
+{
+    if (rc) return fail(call, rc, rt_last_error(c));
+    rt_stats st;
+    rt_last_stats(c, &st);
+    if (n) std::printf("[ETAT]: %zu %s, %s, %.3f ms\n", n, noun, st.kernel, st.kernel_ms);
+    return 0;
+}
+
 // --rays / --hits: the closest hits of the file's rays from context c (either backend).
 static int write_hits(rt_ctx* c, bool cpu, const std::vector<float>& rays, const char* prefix)
 {
-    const uint16_t probe = 1;
-    if (*(const unsigned char*)&probe != 1) return fail("--hits", RT_E_UNSUPPORTED, "little-endian hosts only");
+    if (little_endian("--hits")) return 1;
     const size_t n = rays.size() / 6;
     std::vector<float> t(n), nrm(n * 3);
     std::vector<int32_t> id(n);
@@ -235,10 +251,7 @@ static int write_hits(rt_ctx* c, bool cpu, const std::vector<float>& rays, const
     const int rc = n == 0 ? 0
                    : cpu  ? rt_cpu_trace_rays(c, rays.data(), (int64_t)n, &out)
                           : rt_trace_rays(c, rays.data(), (int64_t)n, &out);
-    if (rc) return fail("rt_trace_rays", rc, rt_last_error(c));
-    rt_stats st;
-    rt_last_stats(c, &st);
-    if (n) std::printf("[ETAT]: %zu rayons, %s, %.3f ms\n", n, st.kernel, st.kernel_ms);
+    if (query_done(c, "rt_trace_rays", rc, n, "rayons")) return 1;
     const std::string p(prefix);
     if (write_npy(p + "_t.npy", "<f4", (int)n, 0, 1, t.data(), n * 4)) return fail("fopen", -1, (p + "_t.npy").c_str());
     if (write_npy(p + "_id.npy", "<i4", (int)n, 0, 1, id.data(), n * 4)) return fail("fopen", -1, (p + "_id.npy").c_str());
@@ -246,39 +259,23 @@ static int write_hits(rt_ctx* c, bool cpu, const std::vector<float>& rays, const
     return 0;
 }
 
-// --segments / --filters: the shadow filters of the file's segments from context c (either backend).
-static int write_filters(rt_ctx* c, bool cpu, const std::vector<float>& segs, const char* path)
+// --segments / --filters (frame null): the shadow filters of the file's segments; --rays / --colours:
+// the colours along the file's rays with frame's parameters.  From context c (either backend), one
+// (N, 3) float32 .npy.
+static int write_n3(rt_ctx* c, bool cpu, const rt_frame* frame, const std::vector<float>& in, const char* path)
 {
-    const uint16_t probe = 1;
-    if (*(const unsigned char*)&probe != 1) return fail("--filters", RT_E_UNSUPPORTED, "little-endian hosts only");
-    const size_t n = segs.size() / 6;
-    std::vector<float> f(n * 3);
-    const int rc = n == 0 ? 0
-                   : cpu  ? rt_cpu_filter_rays(c, segs.data(), (int64_t)n, f.data())
-                          : rt_filter_rays(c, segs.data(), (int64_t)n, f.data());
-    if (rc) return fail("rt_filter_rays", rc, rt_last_error(c));
-    rt_stats st;
-    rt_last_stats(c, &st);
-    if (n) std::printf("[ETAT]: %zu segments, %s, %.3f ms\n", n, st.kernel, st.kernel_ms);
-    if (write_npy(path, "<f4", (int)n, 3, 1, f.data(), n * 12)) return fail("fopen", -1, path);
-    return 0;
-}
-
-// --rays / --colours: the colours along the file's rays from context c (either backend).
-static int write_colours(rt_ctx* c, bool cpu, const rt_frame& frame, const std::vector<float>& rays, const char* path)
-{
-    const uint16_t probe = 1;
-    if (*(const unsigned char*)&probe != 1) return fail("--colours", RT_E_UNSUPPORTED, "little-endian hosts only");
-    const size_t n = rays.size() / 6;
-    std::vector<float> rgb(n * 3);
-    const int rc = n == 0 ? 0
-                   : cpu  ? rt_cpu_shade_rays(c, &frame, rays.data(), (int64_t)n, rgb.data())
-                          : rt_shade_rays(c, &frame, rays.data(), (int64_t)n, rgb.data());
-    if (rc) return fail("rt_shade_rays", rc, rt_last_error(c));
-    rt_stats st;
-    rt_last_stats(c, &st);
-    if (n) std::printf("[ETAT]: %zu rayons, %s, %.3f ms\n", n, st.kernel, st.kernel_ms);
-    if (write_npy(path, "<f4", (int)n, 3, 1, rgb.data(), n * 12)) return fail("fopen", -1, path);
+    if (little_endian(frame ? "--colours" : "--filters")) return 1;
+    const size_t n = in.size() / 6;
+    std::vector<float> out(n * 3);
+    int rc = 0;
+    if (n && frame)
+        rc = cpu ? rt_cpu_shade_rays(c, frame, in.data(), (int64_t)n, out.data())
+                 : rt_shade_rays(c, frame, in.data(), (int64_t)n, out.data());
+    else if (n)
+        rc = cpu ? rt_cpu_filter_rays(c, in.data(), (int64_t)n, out.data())
+                 : rt_filter_rays(c, in.data(), (int64_t)n, out.data());
+    if (query_done(c, frame ? "rt_shade_rays" : "rt_filter_rays", rc, n, frame ? "rayons" : "segments")) return 1;
+    if (write_npy(path, "<f4", (int)n, 3, 1, out.data(), n * 12)) return fail("fopen", -1, path);
     return 0;
 }
 
@@ -677,11 +674,11 @@ int main(int argc, char** argv)
         if (rays_in) {
             std::printf("[ETAT]: Lancer de rayons (%zu rayons de %s)...\n", rays.size() / 6, rays_in);
             if (hits && write_hits(c, cpu, rays, hits)) return 1;
-            if (colours && write_colours(c, cpu, frame, rays, colours)) return 1;
+            if (colours && write_n3(c, cpu, &frame, rays, colours)) return 1;
         }
         if (segs_in) {
             std::printf("[ETAT]: Filtres d'ombre (%zu segments de %s)...\n", segs.size() / 6, segs_in);
-            if (write_filters(c, cpu, segs, filters)) return 1;
+            if (write_n3(c, cpu, nullptr, segs, filters)) return 1;
         }
         if (out) {
             std::vector<uint8_t> img((size_t)W * H * 4);

@@ -192,12 +192,21 @@ def _aov_planes(frame: "Frame", t: bool, id: bool, n: bool):
     return out, aov
 
 
+def _n6(a, what: str):
+    """`a` as a C-order (N, 6) float32 array; `what`: the ValueError's text."""
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != 6:
+        raise ValueError(what)
+    return a
+
+
+_RAYS = "rays: an (N, 6) array [Ox Oy Oz Dx Dy Dz]"
+
+
 def _ray_planes(rays, t: bool, id: bool, n: bool):
     """The (N, 6) float32 ray array, host arrays for the requested planes of N
     entries and the rt_aov that points at them."""
-    r = np.ascontiguousarray(rays, np.float32)
-    if r.ndim != 2 or r.shape[1] != 6:
-        raise ValueError("rays: an (N, 6) array [Ox Oy Oz Dx Dy Dz]")
+    r = _n6(rays, _RAYS)
     count = r.shape[0]
     out = {}
     if t:
@@ -212,17 +221,13 @@ def _ray_planes(rays, t: bool, id: bool, n: bool):
 
 def _segments(segs):
     """The (N, 6) float32 segment array and the (N, 3) float32 array its filters go to."""
-    s = np.ascontiguousarray(segs, np.float32)
-    if s.ndim != 2 or s.shape[1] != 6:
-        raise ValueError("segs: an (N, 6) array [Px Py Pz Lx Ly Lz]")
+    s = _n6(segs, "segs: an (N, 6) array [Px Py Pz Lx Ly Lz]")
     return s, np.zeros((s.shape[0], 3), np.float32)
 
 
 def _shade_rays(rays):
     """The (N, 6) float32 ray array and the (N, 3) float32 array its colours go to."""
-    r = np.ascontiguousarray(rays, np.float32)
-    if r.ndim != 2 or r.shape[1] != 6:
-        raise ValueError("rays: an (N, 6) array [Ox Oy Oz Dx Dy Dz]")
+    r = _n6(rays, _RAYS)
     return r, np.zeros((r.shape[0], 3), np.float32)
 
 
