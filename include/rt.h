@@ -442,6 +442,76 @@ int rt_shade_rays(rt_ctx*, const rt_frame* params, const float* rays, int64_t n,
 int rt_shade_rays_async(rt_ctx*, const rt_frame* params, const float* dev_rays, int64_t n, float* dev_rgb, void* hip_stream);
 int rt_cpu_shade_rays(rt_ctx*, const rt_frame* params, const float* rays, int64_t n, float* rgb);  /* CPU backend */
 
+/* Adaptive supersampling — an addition within ABI 8 (rt_abi_version() stays 8;
+ * test for RT_HAS_ADAPTIVE_SS): s x s samples where neighbouring pixels
+ * disagree and one sample everywhere else, the anti-aliasing of Whitted's own
+ * paper, joined from rt_render_ss, rt_render_aov and rt_shade_rays.
+ * `samples` is the SAMPLE frame exactly as for rt_render_ss (s W x s H, slab
+ * fields in sample rows); the output is W x rt_ss_rows(samples, s), row 0 =
+ * bottom, packed like rt_render_ss's.  Every step is one float32 operation.
+ * Base frame.  B is `samples` with width / s, height / s, inv_w s, inv_h s,
+ * row_begin / s, row_end / s, everything else equal.  For s = 2, 4, 8 the
+ * products are exact, so B's pixels are the sample lattice S[s y][s x] bit for
+ * bit (not so for s = 3, 5, 6, 7: fl(1 / (3 W)) 3 != fl(1 / W); they are
+ * refused).  C(p) is B's float colour of pixel p as rt_render_float(B) gives
+ * it, I(p) and N(p) its rt_render_aov(B) id and normal.
+ * Mask.  mask(p) is the OR, over the 4-neighbours q of p inside the WHOLE
+ * frame [0, W) x [0, H) (a slab changes nothing: its edge rows look at the
+ * rows beyond) and over the requested criteria, of
+ *   RT_EDGE_ID      I(p) != I(q)
+ *   RT_EDGE_NORMAL  exactly one of I(p), I(q) is -1; or both are >= 0 and
+ *                   ((Np.x*Nq.x + Np.y*Nq.y) + Np.z*Nq.z) < normal_cos
+ *   RT_EDGE_COLOUR  fabsf(C(p).c - C(q).c) > colour_delta in some channel
+ *                   (unclamped floats; a NaN compares false: no special case)
+ * Output.  mask(p) == 0: C(p).  Else the box filter of rt_render_ss over the
+ * pixel's s x s samples in its order, sample (i, j) being rt_shade_rays of the
+ * camera ray of sample-frame pixel (s x + i, s y + j) with the frame's
+ * max_bounces, min_energy, scene_ior and background.  RGBA8 is rt_render's
+ * unorm8 of the float; the mask plane holds mask(p) as RT_EDGE_* bits, one
+ * byte per pixel.  So an all-zero mask gives rt_render_float(B) and an
+ * all-set one rt_render_ss_float(samples, s): exactly on the CPU backend, on
+ * the GPU but for the renders' allowance for powf on materials with a
+ * shininess.
+ * rt_render_adaptive is synchronous; each output is independently a host or a
+ * device pointer, or NULL (not all three).  rt_render_adaptive_async takes
+ * device pointers and enqueues on `hip_stream` with rt_render_async's ordering
+ * rules; the base planes and the list of flagged pixels live in buffers of
+ * the context that its streams share, ordered by events and allocated only
+ * when they grow, and no count is read back: the refine kernel
+ * (rt_refine_kernel, csrc/rt_adaptive.h) runs a fixed grid bounded by the
+ * device-resident count.
+ * RT_E_ARG, nothing enqueued and nothing written: s not 2, 4 or 8; s not
+ * dividing width, height, row_begin or row_end; band_rows != 0; criteria zero
+ * or with unknown bits; all three outputs NULL; RT_FLAG_STATS set; a host
+ * pointer given to the async call.  RT_E_STATE: before rt_upload_scene; on
+ * the other backend's context (rt_cpu_render_adaptive is the CPU backend's:
+ * host pointers, the same arithmetic); the async call on a capturing stream
+ * (hipGraph capture is not supported).  RT_E_UNSUPPORTED: as for a render
+ * beyond the deepest compiled stack.
+ * rt_last_stats after the synchronous call: kernel the refine kernel's name
+ * and variant ("rt_refine_kernel<MAXD,1,flags>", rt_shade_rays's variants;
+ * the CPU backend: "cpu_render_adaptive"), kernel_ms base, classify and refine
+ * together, primary_rays = output pixels + s s x flagged output pixels,
+ * stack_depth, everything else 0.  A call that asks for the mask alone (rgba8
+ * and rgb NULL) traces no sample — the refine pass is skipped on both
+ * backends — and reports primary_rays = output pixels. */
+#define RT_HAS_ADAPTIVE_SS 1
+enum { RT_EDGE_ID = 1, RT_EDGE_NORMAL = 2, RT_EDGE_COLOUR = 4 };
+typedef struct rt_adaptive {
+    int32_t s;           /* 2, 4 or 8 */
+    int32_t criteria;    /* RT_EDGE_* bits, at least one */
+    float normal_cos;    /* RT_EDGE_NORMAL */
+    float colour_delta;  /* RT_EDGE_COLOUR */
+} rt_adaptive;
+typedef struct rt_adaptive_out {
+    uint8_t* rgba8;
+    float* rgb;
+    uint8_t* mask;
+} rt_adaptive_out; /* each may be NULL, not all */
+int rt_render_adaptive(rt_ctx*, const rt_frame* samples, const rt_adaptive*, const rt_adaptive_out* out);     /* sync; host or device ptr each */
+int rt_render_adaptive_async(rt_ctx*, const rt_frame* samples, const rt_adaptive*, const rt_adaptive_out* dev, void* hip_stream);
+int rt_cpu_render_adaptive(rt_ctx*, const rt_frame* samples, const rt_adaptive*, const rt_adaptive_out* out); /* CPU backend */
+
 /* ABI 4: context options.  A/B and test switches and tuning knobs; no option
  * changes a single bit of any image.  Upload options take effect at the next
  * rt_upload_scene, launch options at the next render.                      */

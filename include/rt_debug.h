@@ -90,6 +90,12 @@ int rt_debug_selftest(int device, int blocks, unsigned* failures);
 int rt_debug_resolve(rt_ctx*, const float* samples_dev, int width, int s, int rows_out, float* rgb_dev,
                      unsigned* rgba_dev, void* hip_stream);
 
+/* The phases of the last synchronous rt_render_adaptive on the context
+ * (tools/adaptive_probe.py): ms3[0] the base frame and its AOV pass, ms3[1]
+ * classify + scan + scatter, ms3[2] the refine kernel (hipEvents on the
+ * call's stream); *flagged the flagged output pixels.  Either may be NULL. */
+int rt_debug_adaptive_phases(rt_ctx*, float* ms3, unsigned long long* flagged);
+
 /* The launch-camera light records' occupied-direction bounds (RT_OPT_LB_REGION;
  * synchronous): per light j (while 6 j + 5 < n) out[6 j ..] = [a.x, a.y, a.z,
  * cosB, cells of the light's first buffer that hold an entry, violations].  A

@@ -28,6 +28,7 @@
 #include <thread>
 #include <vector>
 
+#include "rt_adaptive.h"
 #include "rt_math.h"
 #include "rt_resolve.h"
 
@@ -516,6 +517,76 @@ void cpu_resolve(const float* samples, int width, int s, int rows_out, uint8_t* 
         }
     }
     if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Adaptive supersampling (rt.h rt_render_adaptive): the base frame with its
+// halo rows and its AOV planes by the two functions above, the shared
+// classification (rt_adaptive.h edge_mask), then only the flagged pixels'
+// samples — trace() of the sample frame's camera rays, resolve_px of the tile.
+int cpu_render_adaptive(const void* handle, int threads, const rt_frame* f, int s, int criteria, float normal_cos,
+                        float colour_delta, uint8_t* rgba, float* rgb, uint8_t* mask, double* ms,
+                        unsigned long long* flagged)
+{
+    using namespace cpu;
+    const Scene& S = *static_cast<const Scene*>(handle);
+    const rt_frame B = adaptive_base(*f, s), Bh = adaptive_halo(B);
+    const int W = B.width, rows = B.row_end - B.row_begin, hrows = Bh.row_end - Bh.row_begin;
+    if (ms) *ms = 0.0;
+    if (flagged) *flagged = 0;
+    if (rows <= 0) return RT_OK;
+    const size_t hpx = (size_t)W * hrows;
+    const bool want_id = (criteria & (kEdgeId | kEdgeNormal)) != 0, want_n = (criteria & kEdgeNormal) != 0;
+    std::vector<float> base(hpx * 3), nrm(want_n ? hpx * 3 : 0);
+    std::vector<int32_t> id(want_id ? hpx : 0);
+    double part = 0.0, total = 0.0;
+    if (int rc = cpu_render(handle, threads, &Bh, hrows, nullptr, base.data(), &part)) return rc;
+    total += part;
+    if (want_id) {
+        if (int rc = cpu_render_aov(handle, threads, &Bh, hrows, nullptr, id.data(), want_n ? nrm.data() : nullptr, &part))
+            return rc;
+        total += part;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const EdgePlanes P{base.data(), want_id ? id.data() : nullptr, want_n ? nrm.data() : nullptr, W, B.height, Bh.row_begin};
+    auto store = [&](size_t o, Color c) {
+        if (rgb) store3(rgb, o, c.r, c.g, c.b);
+        if (rgba) {
+            const unsigned px8 = resolve_rgba8(c);
+            std::memcpy(rgba + 4 * o, &px8, 4);
+        }
+    };
+    std::vector<unsigned> list;  // flagged pixels, row-major
+    for (int q = 0; q < rows; ++q) {
+        const int y = B.row_begin + q;
+        for (int x = 0; x < W; ++x) {
+            const size_t o = (size_t)q * W + x;
+            const int m = edge_mask(P, x, y, criteria, normal_cos, colour_delta);
+            if (mask) mask[o] = (uint8_t)m;
+            if (m) list.push_back((unsigned)o);
+            const float* c = base.data() + 3 * ((size_t)(y - Bh.row_begin) * W + x);
+            store(o, Color{c[0], c[1], c[2]});
+        }
+    }
+    total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const Vec3 O = make3(f->cam_pos[0], f->cam_pos[1], f->cam_pos[2]);
+    const int64_t refine = (rgb || rgba) ? (int64_t)list.size() : 0;  // (a mask alone needs no sample)
+    for_chunks(threads, refine, 16, &part, [&](int64_t k0, int64_t k1) {
+        float tile[kSsMax * kSsMax * 3];
+        for (int64_t k = k0; k < k1; ++k) {
+            const unsigned o = list[(size_t)k];
+            const int x = (int)(o % (unsigned)W), y = B.row_begin + (int)(o / (unsigned)W);
+            for (int j = 0; j < s; ++j)
+                for (int i = 0; i < s; ++i) {
+                    const Color c = trace(S, *f, Ray{O, camera_dir(*f, s * x + i, s * y + j), 1.0f, 1.0f, 0});
+                    store3(tile, (size_t)(j * s + i), c.r, c.g, c.b);
+                }
+            store(o, resolve_px(tile, (size_t)(3 * s), s));
+        }
+    });
+    total += part;
+    if (ms) *ms = total;
+    if (flagged) *flagged = list.size();
+    return RT_OK;
 }
 
 }  // namespace rt

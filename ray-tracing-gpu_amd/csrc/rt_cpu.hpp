@@ -37,6 +37,41 @@ int cpu_shade_rays(const void* handle, int threads, const rt_frame* f, const flo
 // arithmetic): rows_out rows of width / s pixels from their packed sample
 // rows; either output may be null.  *ms = wall time.
 void cpu_resolve(const float* samples, int width, int s, int rows_out, uint8_t* rgba8, float* rgb, double* ms);
+
+// Adaptive supersampling (rt.h rt_render_adaptive*), both backends' frames.
+// The base frame B of sample frame f with factor s (2, 4 or 8, dividing the
+// frame and its slab): the plain frame at W x H whose pixels are the sample
+// lattice S[s y][s x] — inv_w s and inv_h s are exact products of a power of
+// two, and nothing else of the camera depends on the resolution.
+inline rt_frame adaptive_base(const rt_frame& f, int s)
+{
+    rt_frame B = f;
+    B.width = f.width / s;
+    B.height = f.height / s;
+    B.inv_w = f.inv_w * (float)s;
+    B.inv_h = f.inv_h * (float)s;
+    B.row_begin = f.row_begin / s;
+    B.row_end = f.row_end / s;
+    return B;
+}
+// B's slab with the halo: one more row on each side where the frame has one
+// (the flag of a slab's edge row depends on the row beyond it).
+inline rt_frame adaptive_halo(const rt_frame& B)
+{
+    rt_frame h = B;
+    if (B.row_end > B.row_begin) {
+        h.row_begin = B.row_begin > 0 ? B.row_begin - 1 : 0;
+        h.row_end = B.row_end < B.height ? B.row_end + 1 : B.height;
+    }
+    return h;
+}
+// rt_cpu_render_adaptive: the base frame and its AOV planes through cpu_render
+// / cpu_render_aov, rt_adaptive.h's edge_mask per pixel, then the flagged
+// pixels' s x s samples through the pixel loop's own trace and resolve_px.
+// Each output may be null.  *ms = wall time; *flagged = the flagged pixels.
+int cpu_render_adaptive(const void* handle, int threads, const rt_frame* samples, int s, int criteria, float normal_cos,
+                        float colour_delta, uint8_t* rgba8, float* rgb, uint8_t* mask, double* ms,
+                        unsigned long long* flagged);
 }  // namespace rt
 
 #endif  // RT_AMD_RT_CPU_HPP

@@ -950,6 +950,7 @@ __global__ __launch_bounds__(64) void rt_bvh_wave_kernel(const SceneDev S, const
 
 #include "rt_aov.h"  // rt_aov_kernel (needs tile_of_block above)
 #include "rt_shaderays.h"  // rt_shade_rays_kernel (needs radiance and waves_per_eu above)
+#include "rt_adaptive.h"  // rt_edge_classify_kernel, rt_refine_kernel (need radiance and camera_dir above)
 
 // ===================================================================== host
 using namespace rt;
@@ -1181,6 +1182,21 @@ struct rt_ctx : SceneCounts {  // (the uploaded scene's counts: rt_scenehost.h)
         size_t bytes = 0;
         Turn turn;  // left after a call's last resolve
     } ss;
+    // Adaptive supersampling (rt_render_adaptive*): the base frame's planes
+    // with their halo rows (rgb, id, n), the flag words, their offsets, the
+    // list of flagged pixels and the scan's scratch — one allocation per
+    // context, grown on demand and shared by its streams like ss (turn: left
+    // after a call's refine kernel).  ev: the synchronous call's timing —
+    // before the base pass, after it, after classify + scan, after refine.
+    struct AdBuf {
+        void* mem = nullptr;
+        size_t bytes = 0;
+        Turn turn;
+        hipEvent_t ev[4] = {};
+        float phase_ms[3] = {};  // the last synchronous call's (rt_debug_adaptive_phases)
+        const unsigned* total = nullptr;  // the last call's flagged count on the device (the scan's total)
+        unsigned long long flagged = 0;   // read back by the synchronous call, for rt_stats
+    } ad;
     double opt_ss_chunk_rows = 0.0;  // RT_OPT_SS_CHUNK_ROWS (0 = auto)
     int opt_wavefront = 1;      // RT_OPT_WAVEFRONT
     int opt_wf_sort = 1;        // RT_OPT_WF_SORT
@@ -1341,6 +1357,7 @@ static void settled(rt_ctx* c)
     c->state_stream = nullptr;
     c->wf.turn.done();
     c->ss.turn.done();
+    c->ad.turn.done();
     free_deferred(c);
 }
 
@@ -1566,6 +1583,10 @@ RT_EXPORT void rt_destroy(rt_ctx* c)
     hipFree(c->wf.bsum);
     hipFree(c->ss.mem);
     if (c->ss.turn.ev) hipEventDestroy(c->ss.turn.ev);
+    hipFree(c->ad.mem);
+    if (c->ad.turn.ev) hipEventDestroy(c->ad.turn.ev);
+    for (hipEvent_t e : c->ad.ev)
+        if (e) hipEventDestroy(e);
     if (c->wf.turn.ev) hipEventDestroy(c->wf.turn.ev);
     if (c->wf.ev_t) hipEventDestroy(c->wf.ev_t);
     if (c->wf.ev_s) hipEventDestroy(c->wf.ev_s);
@@ -3546,6 +3567,214 @@ RT_EXPORT int rt_cpu_render_ss_float(rt_ctx* c, const rt_frame* f, int32_t s, fl
     return cpu_render_ss_sync(c, f, s, nullptr, rgb_out);
 }
 
+// ---- adaptive supersampling (rt.h rt_render_adaptive*, rt_adaptive.h)
+// The refine kernel for the parameters of f (defined behind the query
+// kernels' table: its instances are named after every other kernel's).
+static int pick_refine(rt_ctx* c, const rt_frame* f, KernelPick& p);
+static const void* edge_kernel(bool scatter);  // rt_edge_classify_kernel / rt_edge_scatter_kernel (named there too)
+static int launch_aov(rt_ctx* c, const rt_frame* f, const rt_aov& dev, hipStream_t st, bool sync_path);
+
+// The checks every adaptive entry point shares (after the backend's own).
+static int adaptive_check(rt_ctx* c, const rt_frame* f, const rt_adaptive* a, const rt_adaptive_out* o)
+{
+    if (int rc = check_uploaded(c, "rt_render_adaptive")) return rc;
+    const char* why = nullptr;
+    if (a->s != 2 && a->s != 4 && a->s != 8)
+        why = "s is 2, 4 or 8";
+    else if (f->band_rows != 0)
+        why = "row bands are not supported";
+    else if (ss_rows_of(f, a->s) < 0)
+        why = "s must divide the sample frame's width, height, row_begin and row_end";
+    else if (a->criteria == 0 || (a->criteria & ~kEdgeAll) != 0)
+        why = "criteria: at least one of RT_EDGE_ID, RT_EDGE_NORMAL, RT_EDGE_COLOUR and nothing else";
+    else if (!o->rgba8 && !o->rgb && !o->mask)
+        why = "no output requested";
+    else if (f->flags & RT_FLAG_STATS)
+        why = "RT_FLAG_STATS is not accepted";
+    else if ((uint64_t)(f->width / a->s) * (uint64_t)ss_rows_of(f, a->s) > (uint64_t)INT32_MAX)
+        why = "more than INT32_MAX output pixels";
+    if (!why) return RT_OK;
+    c->err = std::string("rt_render_adaptive: ") + why;
+    return RT_E_ARG;
+}
+
+// One adaptive render of sample frame f on st into device planes (each may be
+// null).  sync_path: rt_render_adaptive on c->stream, timed by c->ad.ev.
+//  1. the base frame B with its halo rows through launch and launch_aov,
+//     unchanged, into the context's planes (the AOV pass only for RT_EDGE_ID /
+//     RT_EDGE_NORMAL, its normals only for RT_EDGE_NORMAL);
+//  2. rt_edge_classify_kernel: masks, flags and the base colours; scan_u32 of
+//     the flags; rt_edge_scatter_kernel: the row-major list of flagged pixels;
+//  3. rt_refine_kernel on a fixed grid, bounded by the scan's total on the
+//     device.
+static int launch_adaptive(rt_ctx* c, const rt_frame* f, const rt_adaptive* a, const KernelPick& kp, unsigned* rgba,
+                           float* rgb, unsigned char* mask, hipStream_t st, bool sync_path)
+{
+    const int s = a->s, ls = s == 2 ? 1 : (s == 4 ? 2 : 3);
+    const rt_frame B = adaptive_base(*f, s), Bh = adaptive_halo(B);
+    const int W = B.width, rows = B.row_end - B.row_begin, hrows = Bh.row_end - Bh.row_begin;
+    rt_ctx::AdBuf& A = c->ad;
+    A.flagged = 0;
+    if (rows <= 0) return RT_OK;
+    const size_t n = (size_t)W * rows, hpx = (size_t)W * hrows;
+    const bool want_id = (a->criteria & (kEdgeId | kEdgeNormal)) != 0, want_n = (a->criteria & kEdgeNormal) != 0;
+    size_t need = 0;
+    auto part = [&](size_t bytes) {
+        const size_t o = need;
+        need += (bytes + 255) / 256 * 256;
+        return o;
+    };
+    const size_t o_rgb = part(hpx * 12), o_id = part(want_id ? hpx * 4 : 0), o_n = part(want_n ? hpx * 12 : 0),
+                 o_flag = part(n * 4), o_off = part((n + 1) * 4), o_list = part(n * 4),
+                 o_scan = part(scan_scratch(n) * sizeof(unsigned long long));
+    if (need > A.bytes) {
+        free_later(c, A.mem);  // an enqueued call may still use the old one
+        A.mem = nullptr;
+        A.bytes = 0;
+        HIP_TRY(c, hipMalloc(&A.mem, need));
+        A.bytes = need;
+    }
+    char* const m = (char*)A.mem;
+    float* const p_rgb = (float*)(m + o_rgb);
+    int32_t* const p_id = want_id ? (int32_t*)(m + o_id) : nullptr;
+    float* const p_n = want_n ? (float*)(m + o_n) : nullptr;
+    unsigned* const flag = (unsigned*)(m + o_flag);
+    unsigned* const off = (unsigned*)(m + o_off);
+    unsigned* const list = (unsigned*)(m + o_list);
+    A.total = off + n;
+    if (sync_path)
+        for (hipEvent_t& e : A.ev)
+            if (!e) HIP_TRY(c, hipEventCreate(&e));
+    if (int rc = A.turn.enter(c, st)) return rc;
+    const auto enqueue = [&]() -> int {
+        if (sync_path) HIP_TRY(c, hipEventRecord(A.ev[0], st));
+        if (int rc = launch(c, &Bh, nullptr, p_rgb, st, false, sync_path)) return rc;
+        if (want_id)
+            if (int rc = launch_aov(c, &Bh, rt_aov{nullptr, p_id, p_n}, st, sync_path)) return rc;
+        if (sync_path) HIP_TRY(c, hipEventRecord(A.ev[1], st));
+        const EdgePlanes P{p_rgb, p_id, p_n, W, B.height, Bh.row_begin};
+        const unsigned nn = (unsigned)n, blocks = (unsigned)((n + 255) / 256);
+        {
+            EdgePlanes Pv = P;
+            int rb = B.row_begin, crit = a->criteria;
+            unsigned nv = nn;
+            float cosv = a->normal_cos, delta = a->colour_delta;
+            unsigned* fl = flag;
+            void* args[] = {&Pv, &rb, &nv, &crit, &cosv, &delta, &fl, &rgb, &rgba, &mask};
+            HIP_TRY(c, hipLaunchKernel(edge_kernel(false), dim3(blocks), dim3(256), args, 0, st));
+        }
+        HIP_TRY(c, scan_u32(flag, nn, off, (unsigned long long*)(m + o_scan), st, nullptr));
+        {
+            const unsigned *fl = flag, *of = off;
+            unsigned nv = nn;
+            unsigned* ls_ = list;
+            void* args[] = {&fl, &of, &nv, &ls_};
+            HIP_TRY(c, hipLaunchKernel(edge_kernel(true), dim3(blocks), dim3(256), args, 0, st));
+        }
+        if (sync_path) HIP_TRY(c, hipEventRecord(A.ev[2], st));
+        if (rgb || rgba) {  // (a mask alone needs no sample)
+            // (after the base passes: they may have allocated the camera state scene_dev names)
+            SceneDev S = scene_dev(c, c->cam, has_light_buf(kp.v.flags), false);
+            FrameDev F;
+            frame_dev(f, F);
+            const unsigned* lst = list;
+            const unsigned* total = A.total;
+            int lsv = ls, wo = W, rb = B.row_begin;
+            const size_t per = (size_t)64 >> (2 * ls);
+            const unsigned grid = (unsigned)std::min<size_t>(kRefineGrid, (n + per - 1) / per);
+            void* args[] = {&S, &F, &lst, &total, &lsv, &wo, &rb, &rgb, &rgba};
+            HIP_TRY(c, hipLaunchKernel(kp.k, dim3(grid), dim3(64), args, kp.lds, st));
+        }
+        if (sync_path) HIP_TRY(c, hipEventRecord(A.ev[3], st));
+        return RT_OK;
+    };
+    // (the turn is left behind a failure too: what was enqueued before it still uses the planes)
+    const int rc = enqueue(), left = A.turn.leave(c, st);
+    return rc ? rc : left;
+}
+
+RT_EXPORT int rt_render_adaptive(rt_ctx* c, const rt_frame* f, const rt_adaptive* a, const rt_adaptive_out* out)
+{
+    if (!c || !f || !a || !out) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    if (int rc = adaptive_check(c, f, a, out)) return rc;
+    KernelPick kp;
+    if (int rc = pick_refine(c, f, kp)) return rc;
+    if (int rc = sync_begin(c)) return rc;
+    const size_t px = (size_t)(f->width / a->s) * (size_t)ss_rows_of(f, a->s);
+    // (one 256-byte aligned part of the scratch per host plane)
+    SyncOut o;
+    const size_t bytes[3] = {px * 4, px * 12, px};
+    void* const user[3] = {out->rgba8, out->rgb, out->mask};
+    for (int i = 0; i < 3; ++i) o.add(user[i], (bytes[i] + 255) / 256 * 256);
+    if (int rc = o.place(c)) return rc;
+    if (int rc = launch_adaptive(c, f, a, kp, (unsigned*)o.target[0], (float*)o.target[1], (unsigned char*)o.target[2],
+                                 c->stream, true))
+        return rc;
+    for (int i = 0; i < 3; ++i)
+        if (int rc = o.copy_back(c, i, bytes[i])) return rc;
+    if (int rc = finish_sync(c, f, c->stream, false)) return rc;
+    rt_ctx::AdBuf& A = c->ad;
+    c->last = rt_stats{};
+    std::memcpy(c->last.kernel, kp.name->s, sizeof kp.name->s);
+    c->last.stack_depth = kp.v.maxd;
+    if (px) {
+        unsigned flagged = 0;  // (for the stats only: no launch was sized by it)
+        HIP_TRY(c, hipMemcpy(&flagged, A.total, sizeof flagged, hipMemcpyDeviceToHost));
+        A.flagged = flagged;
+        float ms = 0.f;
+        for (int i = 0; i < 3; ++i) {
+            HIP_TRY(c, hipEventElapsedTime(&A.phase_ms[i], A.ev[i], A.ev[i + 1]));
+            ms += A.phase_ms[i];
+        }
+        c->last.kernel_ms = ms;
+    }
+    // (a mask alone traces no sample)
+    c->last.primary_rays = (uint64_t)px + ((out->rgba8 || out->rgb) ? (uint64_t)(a->s * a->s) * A.flagged : 0);
+    return RT_OK;
+}
+
+RT_EXPORT int rt_render_adaptive_async(rt_ctx* c, const rt_frame* f, const rt_adaptive* a, const rt_adaptive_out* dev,
+                                       void* stream)
+{
+    if (!c || !f || !a || !dev) return RT_E_ARG;
+    if (c->cpu) return not_cpu(c);
+    if (int rc = adaptive_check(c, f, a, dev)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    for (const void* p : {(const void*)dev->rgba8, (const void*)dev->rgb, (const void*)dev->mask})
+        if (p && !is_device_ptr(p)) {
+            c->err = "rt_render_adaptive_async takes device pointers";
+            return RT_E_ARG;
+        }
+    const hipStream_t st = (hipStream_t)stream;
+    bool capturing = false;
+    if (int rc = stream_capturing(c, st, &capturing)) return rc;
+    if (capturing) {
+        c->err = "rt_render_adaptive_async: hipGraph capture is not supported";
+        return RT_E_STATE;
+    }
+    KernelPick kp;
+    if (int rc = pick_refine(c, f, kp)) return rc;
+    return launch_adaptive(c, f, a, kp, (unsigned*)dev->rgba8, dev->rgb, dev->mask, st, false);
+}
+
+RT_EXPORT int rt_cpu_render_adaptive(rt_ctx* c, const rt_frame* f, const rt_adaptive* a, const rt_adaptive_out* out)
+{
+    if (!c || !f || !a || !out) return RT_E_ARG;
+    if (!c->cpu) return needs_cpu(c, "rt_cpu_render_adaptive");
+    if (int rc = adaptive_check(c, f, a, out)) return rc;
+    c->last = rt_stats{};
+    double ms = 0.0;
+    unsigned long long flagged = 0;
+    const int rc = cpu_render_adaptive(c->cpu_scene, c->cpu_threads, f, a->s, a->criteria, a->normal_cos,
+                                       a->colour_delta, out->rgba8, out->rgb, out->mask, &ms, &flagged);
+    c->last.kernel_ms = (float)ms;
+    c->last.primary_rays = (uint64_t)(f->width / a->s) * (uint64_t)ss_rows_of(f, a->s) +
+                           ((out->rgba8 || out->rgb) ? (uint64_t)(a->s * a->s) * flagged : 0);
+    std::snprintf(c->last.kernel, sizeof c->last.kernel, "cpu_render_adaptive");
+    return rc;
+}
+
 // ---- primary-hit AOV renders (rt.h, rt_aov.h)
 #define RT_V(M, L, F) {{M, L, F}, {(const void*)&rt_aov_kernel<F>}, kernel_name("rt_aov_kernel", F)},
 static const KernelRow<1> kAovKernels[] = {RT_AOV_VARIANTS};
@@ -3914,7 +4143,8 @@ static const KernelRow<1> kShadeRaysKernels[] = {RT_SHADE_RAYS_VARIANTS};
 
 // The query's kernel for the parameters of f: select_query_variant's row
 // (k == nullptr: the reachable depth exceeds the compiled stacks).
-static int pick_shade_rays(rt_ctx* c, const rt_frame* f, KernelPick& p)
+template <size_t ROWS>
+static int pick_query_row(rt_ctx* c, const rt_frame* f, const KernelRow<1> (&table)[ROWS], KernelPick& p)
 {
     QueryFacts q;
     q.depth = reachable_depth(c, f);
@@ -3923,7 +4153,7 @@ static int pick_shade_rays(rt_ctx* c, const rt_frame* f, KernelPick& p)
     q.bvh = rays_bvh(c);
     p = KernelPick{};
     p.v = select_query_variant(q);
-    if (const KernelRow<1>* r = find_row(kShadeRaysKernels, p.v)) {
+    if (const KernelRow<1>* r = find_row(table, p.v)) {
         p.k = r->k[0];
         p.name = &r->name;
         p.lds = lds_bytes(p.v.flags, c->bvh_depth);
@@ -3931,6 +4161,22 @@ static int pick_shade_rays(rt_ctx* c, const rt_frame* f, KernelPick& p)
     }
     c->err = "reachable bounce depth " + std::to_string(q.depth) + " exceeds the compiled stack (32)";
     return RT_E_UNSUPPORTED;
+}
+static int pick_shade_rays(rt_ctx* c, const rt_frame* f, KernelPick& p)
+{
+    return pick_query_row(c, f, kShadeRaysKernels, p);
+}
+
+// The refine kernels of the adaptive renders (rt_adaptive.h): the query's
+// variants, selected the same way; s is a launch argument.  Named here, behind
+// every other table, so that the code object keeps the other kernels' order.
+#define RT_V(M, L, F) {{M, L, F}, {(const void*)&rt_refine_kernel<M, L, F>}, kernel_name("rt_refine_kernel", M, L, F)},
+static const KernelRow<1> kRefineKernels[] = {RT_SHADE_RAYS_VARIANTS};
+#undef RT_V
+static int pick_refine(rt_ctx* c, const rt_frame* f, KernelPick& p) { return pick_query_row(c, f, kRefineKernels, p); }
+static const void* edge_kernel(bool scatter)
+{
+    return scatter ? (const void*)&rt_edge_scatter_kernel<0> : (const void*)&rt_edge_classify_kernel<0>;
 }
 
 // n rays into d_rgb on st: one kernel, no state of the context besides the
@@ -3993,6 +4239,15 @@ RT_EXPORT int rt_debug_resolve(rt_ctx* c, const float* samples, int width, int s
     if (c->cpu) return not_cpu(c);
     HIP_TRY(c, hipSetDevice(c->device));
     return launch_resolve(c, samples, width, s, rows_out, rgb, rgba, (hipStream_t)stream);
+}
+
+// Diagnostic (include/rt_debug.h): the last synchronous adaptive render's phases.
+RT_EXPORT int rt_debug_adaptive_phases(rt_ctx* c, float* ms3, unsigned long long* flagged)
+{
+    if (!c) return RT_E_ARG;
+    if (ms3) std::memcpy(ms3, c->ad.phase_ms, sizeof c->ad.phase_ms);
+    if (flagged) *flagged = c->ad.flagged;
+    return RT_OK;
 }
 
 RT_EXPORT int rt_last_stats(rt_ctx* c, rt_stats* out)

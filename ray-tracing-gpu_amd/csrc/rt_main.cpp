@@ -6,6 +6,7 @@
 //             [--ssaa N] [--aov PREFIX] [--rays IN.npy --hits PREFIX [--ray-bvh]]
 //             [--segments IN.npy --filters OUT.npy [--ray-bvh]]
 //             [--rays IN.npy --colours OUT.npy [-d N] [--ray-bvh]]
+//             [--adaptive N [--edge id,normal,colour] [--edge-cos X] [--edge-delta X] [--mask OUT.npy]]
 //
 // Kept from Main.cpp:51-199: argv[1] is the scene file, -x / -y set the
 // resolution (default 512x256, Var.cpp:4-5), the same [ETAT]/[ERREUR] log
@@ -56,6 +57,14 @@
 // rays (rt_shade_rays / rt_cpu_shade_rays) with the scene's parameters and
 // -d's bounce depth: OUT.npy is float32 (N, 3).  Alone or beside --hits; the
 // same rules as --hits.
+// --adaptive N (2, 4 or 8) writes the W x H image with adaptive supersampling
+// (rt_render_adaptive / rt_cpu_render_adaptive: the scene is prepared at
+// N W x N H as for --ssaa): N x N samples only where a pixel differs from a
+// 4-neighbour by one of --edge's criteria (default id,normal,colour; --edge-cos
+// the normals' cosine, default 0.9; --edge-delta the colour step, default
+// 0.1), one sample elsewhere.  --mask OUT.npy also writes the criteria that
+// flagged each pixel (uint8, H x W, RT_EDGE_* bits, row 0 = the bottom
+// scanline).  On either backend, one GPU; not with --ssaa, --aov or the queries.
 #include <hip/hip_runtime_api.h>
 
 #include <dlfcn.h>
@@ -519,6 +528,10 @@ int main(int argc, char** argv)
     const char* colours = nullptr;
     const char* segs_in = nullptr;
     const char* filters = nullptr;
+    int adaptive = 0, edge = RT_EDGE_ID | RT_EDGE_NORMAL | RT_EDGE_COLOUR;
+    bool adaptive_given = false;
+    float edge_cos = 0.9f, edge_delta = 0.1f;
+    const char* mask_out = nullptr;
     for (int i = 2; i < argc; ++i) {
         if (argv[i][0] != '-') continue;
         auto next = [&](int& v) {
@@ -536,6 +549,40 @@ int main(int argc, char** argv)
         if (std::strcmp(argv[i], "--ssaa") == 0) {
             ssaa = 0;
             next(ssaa);
+            continue;
+        }
+        if (std::strcmp(argv[i], "--adaptive") == 0) {
+            adaptive_given = true;
+            next(adaptive);
+            continue;
+        }
+        if (std::strcmp(argv[i], "--edge") == 0) {
+            std::string list = i + 1 < argc ? argv[++i] : "";
+            edge = 0;
+            for (size_t a = 0; a <= list.size();) {
+                const size_t b = std::min(list.find(',', a), list.size());
+                const std::string w = list.substr(a, b - a);
+                if (w == "id")
+                    edge |= RT_EDGE_ID;
+                else if (w == "normal")
+                    edge |= RT_EDGE_NORMAL;
+                else if (w == "colour")
+                    edge |= RT_EDGE_COLOUR;
+                else
+                    return fail("arguments", RT_E_ARG, "--edge is a comma-separated list of id, normal, colour");
+                a = b + 1;
+            }
+            continue;
+        }
+        if (std::strcmp(argv[i], "--edge-cos") == 0 || std::strcmp(argv[i], "--edge-delta") == 0) {
+            if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--edge-cos / --edge-delta need a number");
+            (argv[i][7] == 'c' ? edge_cos : edge_delta) = (float)std::atof(argv[i + 1]);
+            ++i;
+            continue;
+        }
+        if (std::strcmp(argv[i], "--mask") == 0) {
+            if (i + 1 >= argc) return fail("arguments", RT_E_ARG, "--mask needs a .npy file to write");
+            mask_out = argv[++i];
             continue;
         }
         if (std::strcmp(argv[i], "--aov") == 0) {
@@ -617,6 +664,13 @@ int main(int argc, char** argv)
     if (ssaa > 1 && (gpus != 1 || bands || gather == 1))
         return fail("arguments", RT_E_ARG,
                     "--ssaa renders on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
+    if (adaptive_given && adaptive != 2 && adaptive != 4 && adaptive != 8)
+        return fail("arguments", RT_E_ARG, "--adaptive is 2, 4 or 8");
+    if (adaptive_given && (ssaa > 1 || aov || rays_in || segs_in || gpus != 1 || bands || gather == 1))
+        return fail("arguments", RT_E_ARG,
+                    "--adaptive renders on one GPU: it cannot be combined with --ssaa, --aov, --rays, --segments, -g "
+                    "above 1, --bands or --gather rccl");
+    if (mask_out && !adaptive_given) return fail("arguments", RT_E_ARG, "--mask goes with --adaptive");
     if (aov && (gpus != 1 || bands || gather == 1))
         return fail("arguments", RT_E_ARG,
                     "--aov renders on one GPU: it cannot be combined with -g above 1, --bands or --gather rccl");
@@ -649,7 +703,8 @@ int main(int argc, char** argv)
     rt_scene* scene = nullptr;
     int rc = rt_scene_create(&scene);
     if (rc) return fail("rt_scene_create", rc, "");
-    rt_scene_set_resolution(scene, W * ssaa, H * ssaa);  // (--ssaa: the sample grid)
+    const int grid = adaptive_given ? adaptive : ssaa;
+    rt_scene_set_resolution(scene, W * grid, H * grid);  // (--ssaa, --adaptive: the sample grid)
     rt_scene_set_max_bounces(scene, depth);
     std::printf("[ETAT]: Traitement du fichier de donnees de la scene...\n");
     if ((rc = rt_scene_load_file(scene, argv[1]))) return fail("TraiterFichierDeScene", rc, rt_scene_error(scene));
@@ -660,6 +715,41 @@ int main(int argc, char** argv)
     rt_scene_get_frame(scene, &frame);
     if (stats) frame.flags |= RT_FLAG_STATS;
 
+    if (adaptive_given) {  // one context of either backend, the sample frame refined where its pixels disagree
+        if (little_endian("--adaptive")) return 1;
+        rt_ctx* c = nullptr;
+        if (cpu) {
+            if ((rc = rt_create_cpu(threads, &c))) return fail("rt_create_cpu", rc, "");
+        } else {
+            int nd = 0;
+            if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return fail("rt_create", RT_E_HIP, "no HIP device");
+            if ((rc = rt_create(dev0 % nd, &c))) return fail("rt_create", rc, c ? rt_last_error(c) : "");
+        }
+        if ((rc = rt_upload_scene(c, &flat))) return fail("rt_upload_scene", rc, rt_last_error(c));
+        frame.flags &= ~RT_FLAG_STATS;  // (not accepted by the adaptive render: its rt_stats carry the ray count)
+        std::vector<uint8_t> img((size_t)W * H * 4), mask((size_t)W * H);
+        const rt_adaptive how{adaptive, edge, edge_cos, edge_delta};
+        const rt_adaptive_out to{img.data(), nullptr, mask.data()};
+        std::printf("[ETAT]: Lancer de rayons (adaptatif, %d x %d echantillons par pixel de contour)...\n", adaptive,
+                    adaptive);
+        double total = 0.0;
+        for (int k = 0; k < frames; ++k) {
+            const auto t0 = std::chrono::steady_clock::now();
+            if ((rc = cpu ? rt_cpu_render_adaptive(c, &frame, &how, &to) : rt_render_adaptive(c, &frame, &how, &to)))
+                return fail("LancerRayons", rc, rt_last_error(c));
+            total += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        size_t flagged = 0;
+        for (uint8_t m : mask) flagged += m != 0;
+        std::printf("[ETAT]: %zu pixels de contour sur %zu (%.1f %%)\n", flagged, mask.size(),
+                    100.0 * (double)flagged / (double)mask.size());
+        print_done(c, total, frames, 1, 0, stats);
+        if (out && write_ppm(out, W, H, img)) return fail("fopen", -1, out);
+        if (mask_out && write_npy(mask_out, "|u1", H, W, 1, mask.data(), mask.size())) return fail("fopen", -1, mask_out);
+        rt_destroy(c);
+        rt_scene_destroy(scene);
+        return 0;
+    }
     if (rays_in || segs_in) {  // ray / filter queries: one context of either backend; the frame only for -o
         rt_ctx* c = nullptr;
         if (cpu) {

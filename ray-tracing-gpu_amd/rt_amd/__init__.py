@@ -24,7 +24,8 @@ import numpy as np
 
 __all__ = [
     "RtError", "SceneFlat", "Frame", "Stats", "Aov", "Scene", "Context", "CpuContext", "CScene", "lib", "band_rows",
-    "frame_rows", "ss_rows", "SS_OPTIONS", "LB_OPTIONS", "RAY_OPTIONS",
+    "frame_rows", "ss_rows", "SS_OPTIONS", "LB_OPTIONS", "RAY_OPTIONS", "Adaptive", "AdaptiveOut",
+    "EDGE_ID", "EDGE_NORMAL", "EDGE_COLOUR",
     "LIB_PATH", "TRIANGLE", "PLANE", "QUADRIC", "FLAG_STATS", "OPTIONS", "camera_path",
 ]
 
@@ -33,6 +34,7 @@ LIB_PATH = os.environ.get("RT_AMD_LIB", os.path.join(os.path.dirname(_HERE), "li
 
 TRIANGLE, PLANE, QUADRIC = 0, 1, 2
 FLAG_STATS = 1
+EDGE_ID, EDGE_NORMAL, EDGE_COLOUR = 1, 2, 4  # rt.h RT_EDGE_*: the criteria of the adaptive renders
 # rt.h RT_OPT_* (ABI 5): A/B and test switches, none changes an image bit
 OPTIONS = {"light_buffer": 1, "camera_buffer": 2, "union_pretest": 3, "lb_scale": 4, "dcov_near": 5,
            "cb_inline_max_mb": 6, "host_chunk_mb": 7, "cb_capacity": 8, "launch_camera": 12, "bvh": 13, "wavefront": 14,
@@ -96,6 +98,17 @@ class Aov(ctypes.Structure):
     _fields_ = [("t", ctypes.c_void_p), ("id", ctypes.c_void_p), ("n", ctypes.c_void_p)]
 
 
+class Adaptive(ctypes.Structure):
+    """rt.h rt_adaptive: the factor (2, 4 or 8), the RT_EDGE_* criteria and their thresholds."""
+    _fields_ = [("s", ctypes.c_int32), ("criteria", ctypes.c_int32), ("normal_cos", ctypes.c_float),
+                ("colour_delta", ctypes.c_float)]
+
+
+class AdaptiveOut(ctypes.Structure):
+    """rt.h rt_adaptive_out: the requested outputs (a null pointer: not requested)."""
+    _fields_ = [("rgba8", ctypes.c_void_p), ("rgb", ctypes.c_void_p), ("mask", ctypes.c_void_p)]
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 # Every symbol include/rt.h declares, with its ctypes signature.
@@ -124,6 +137,12 @@ SIGNATURES = {
     "rt_cpu_render_ss": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.c_int32, _VP]),
     "rt_cpu_render_ss_float": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.c_int32, _VP]),
     "rt_ss_rows": (ctypes.c_int32, [ctypes.POINTER(Frame), ctypes.c_int32]),
+    "rt_render_adaptive": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Adaptive),
+                                          ctypes.POINTER(AdaptiveOut)]),
+    "rt_render_adaptive_async": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Adaptive),
+                                                ctypes.POINTER(AdaptiveOut), _VP]),
+    "rt_cpu_render_adaptive": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Adaptive),
+                                              ctypes.POINTER(AdaptiveOut)]),
     "rt_render_aov": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Aov)]),
     "rt_render_aov_async": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Aov), _VP]),
     "rt_cpu_render_aov": (ctypes.c_int, [_VP, ctypes.POINTER(Frame), ctypes.POINTER(Aov)]),
@@ -190,6 +209,20 @@ def _aov_planes(frame: "Frame", t: bool, id: bool, n: bool):
         out["n"] = np.zeros((rows, w, 3), np.float32)
     aov = Aov(*(out[k].ctypes.data if k in out else None for k in ("t", "id", "n")))
     return out, aov
+
+
+def _adaptive(frame: "Frame", s: int, criteria: int, normal_cos: float, colour_delta: float):
+    """Host arrays for the three outputs of an adaptive render of the sample
+    frame `frame`, and the rt_adaptive / rt_adaptive_out that describe it.  A
+    pair (frame, s) the call would refuse gives empty arrays: the call reports it."""
+    rows = lib().rt_ss_rows(ctypes.byref(frame), int(s)) if int(s) > 0 else -1
+    h, w = (rows, frame.width // int(s)) if rows >= 0 else (0, 0)
+    out = {"rgb": np.zeros((h, w, 3), np.float32), "rgba": np.zeros((h, w, 4), np.uint8),
+           "mask": np.zeros((h, w), np.uint8)}
+    a = Adaptive(int(s), int(criteria), float(normal_cos), float(colour_delta))
+    # (an empty array's address still is a non-null pointer: the call checks its arguments, not these)
+    o = AdaptiveOut(out["rgba"].ctypes.data, out["rgb"].ctypes.data, out["mask"].ctypes.data)
+    return out, a, o
 
 
 def _n6(a, what: str):
@@ -407,6 +440,28 @@ class Context:
         _check("rt_render_ss_async", lib().rt_render_ss_async(self._h, ctypes.byref(frame), s, rgba_dev_ptr or None,
                                                               rgb_dev_ptr or None, stream or None), self._err)
 
+    def render_adaptive(self, frame: Frame, s: int, criteria: int, normal_cos: float = 0.9,
+                        colour_delta: float = 0.1) -> dict:
+        """rt_render_adaptive: `frame` is the SAMPLE frame (s W x s H, s = 2, 4
+        or 8); pixels that an EDGE_* criterion separates from a 4-neighbour are
+        resolved from their s x s samples, the others keep the plain W x H
+        frame's colour.  Returns {"rgb": (rows, W, 3) float32, "rgba": (rows, W,
+        4) uint8, "mask": (rows, W) uint8 of EDGE_* bits}, row 0 = bottom."""
+        out, a, o = _adaptive(frame, s, criteria, normal_cos, colour_delta)
+        _check("rt_render_adaptive", lib().rt_render_adaptive(self._h, ctypes.byref(frame), ctypes.byref(a),
+                                                              ctypes.byref(o)), self._err)
+        return out
+
+    def render_adaptive_async(self, frame: Frame, s: int, criteria: int, normal_cos: float = 0.9,
+                              colour_delta: float = 0.1, rgba_dev_ptr: int = 0, rgb_dev_ptr: int = 0,
+                              mask_dev_ptr: int = 0, stream: int = 0):
+        """rt_render_adaptive_async: device pointers to the outputs (0: not requested), enqueued on `stream`."""
+        a = Adaptive(int(s), int(criteria), float(normal_cos), float(colour_delta))
+        o = AdaptiveOut(rgba_dev_ptr or None, rgb_dev_ptr or None, mask_dev_ptr or None)
+        _check("rt_render_adaptive_async",
+               lib().rt_render_adaptive_async(self._h, ctypes.byref(frame), ctypes.byref(a), ctypes.byref(o),
+                                              stream or None), self._err)
+
     def render_aov(self, frame: Frame, t: bool = True, id: bool = True, n: bool = True) -> dict:
         """rt_render_aov: the primary hit of every pixel, no shading.  Returns
         the requested planes: "t" (rows, W) float32, "id" (rows, W) int32 (file
@@ -550,6 +605,14 @@ class CpuContext:
                lib().rt_cpu_render_ss_float(self._h, ctypes.byref(frame), s, out.ctypes.data), self._err)
         return out
 
+    def render_adaptive(self, frame: Frame, s: int, criteria: int, normal_cos: float = 0.9,
+                        colour_delta: float = 0.1) -> dict:
+        """rt_cpu_render_adaptive: as Context.render_adaptive, on host threads."""
+        out, a, o = _adaptive(frame, s, criteria, normal_cos, colour_delta)
+        _check("rt_cpu_render_adaptive", lib().rt_cpu_render_adaptive(self._h, ctypes.byref(frame), ctypes.byref(a),
+                                                                      ctypes.byref(o)), self._err)
+        return out
+
     def render_aov(self, frame: Frame, t: bool = True, id: bool = True, n: bool = True) -> dict:
         """rt_cpu_render_aov: as Context.render_aov, on host threads (the same bits)."""
         out, aov = _aov_planes(frame, t, id, n)
@@ -666,6 +729,15 @@ class CScene:
         """m_InfoPixel equivalent: float32 (H, W, 3), unclamped."""
         f = self._frame()
         return self._ctx.render_float(f) if self._ss == 1 else self._ctx.render_ss_float(f, self._ss)
+
+    def LancerRayonsAdaptatif(self, criteria: int = EDGE_ID | EDGE_NORMAL | EDGE_COLOUR, normal_cos: float = 0.9,
+                              colour_delta: float = 0.1) -> dict:
+        """The frame with adaptive supersampling (not in the reference): with
+        AjusterSurEchantillonnage(s), s = 2, 4 or 8, only the pixels on an edge
+        (EDGE_* criteria) are resolved from s x s samples.  Returns {"rgb",
+        "rgba", "mask"} as Context.render_adaptive returns them."""
+        f = self._frame()
+        return self._ctx.render_adaptive(f, self._ss, criteria, normal_cos, colour_delta)
 
     def LancerRayonsAOV(self) -> dict:
         """The primary-hit buffers of the frame LancerRayons renders (not in
